@@ -232,6 +232,7 @@ def infer_main(args):
     a = C_.recipe_args("base_recipe")
     task = tasks.S2ST_TranslationTask.setup_task(a, device=dev)
     torch.manual_seed(1)
+    np.random.seed(1)  # the Griffin-Lim initial phases come from numpy's global generator: the same draws every run
     model = task.build_model(a)  # random-init weights of the architecture (no checkpoints on the box)
     voc_kw = dict(sample_rate=24000, win_size=1200, hop_size=300, n_fft=2048, n_mels=80, f_min=20, f_max=8000)
     voc = V.GriffinLimVocoder(spec_bwd_max_iter=INFER_GL_ITERS, device=dev, **voc_kw)
@@ -259,6 +260,8 @@ def infer_main(args):
     # next batches' do not depend on them.  Same hypotheses as one batch after the other (tests/test_inference.py).
     CHAINS = importlib.import_module(PKG + ".runtime.streams").default_decode_chains()
 
+    last_hypos = []  # the hypotheses of the last step of the last run() (--dump-outputs)
+
     def run(gen_list, n_steps, first=0):
         held, n_u, n_f = [], 0, 0
 
@@ -268,6 +271,8 @@ def infer_main(args):
                 h.wait()
                 n_u += len(h)
                 n_f += sum(int(f["feature"].shape[0]) for f in h)
+            if held:
+                last_hypos[:] = held[-1]
             held.clear()
 
         i = first
@@ -296,6 +301,12 @@ def infer_main(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vlog("timed region", dt, "s for", n_utt, "utterances")
+    if args.dump_outputs:
+        # the last timed batch's hypotheses, every per-utterance tensor concatenated over the utterances in batch order
+        keys = [k for k, v in last_hypos[0].items() if torch.is_tensor(v) and v.is_floating_point()]
+        arrays = {k: torch.cat([h[k].reshape(-1) for h in last_hypos]) for k in keys}
+        arrays["lengths"] = torch.tensor([float(h["feature"].shape[0]) for h in last_hypos], dtype=torch.float64)
+        dump_outputs(args.dump_outputs, arrays)
     # the same pass with the initial phases drawn by the device's generator instead of numpy's (GriffinLim(phase_rng="device"):
     # same distribution, no host-side generator run) -- reported next to `value`, never as it
     voc_d = V.GriffinLimVocoder(spec_bwd_max_iter=INFER_GL_ITERS, device=dev, phase_rng="device", **voc_kw)
@@ -487,6 +498,32 @@ def infer_main(args):
 # boxes (profiles/r06_adam_overlap_ab.txt) and is the default of bench.py and train.py; S2ST_ADAM_OVERLAP=0 switches it off.
 ADAM_OVERLAP = os.environ.get("S2ST_ADAM_OVERLAP", "1") != "0"
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 1 << 20      # --dump-outputs: a larger array is written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """--dump-outputs: write ``{name: tensor}`` as ``out_dir/<name>.npy`` (float64 stays float64, everything else becomes
+    float32).  An array of more than DUMP_MAX_ELEMS elements is flattened and sampled at indices drawn (with replacement,
+    sorted) by a CPU generator seeded from its element count: two builds run with the same arguments write the same
+    positions."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(t.numel())
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[name] = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes over {len(out)} arrays exceed {DUMP_BUDGET_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    vlog("dumped", len(out), "arrays,", total, "bytes, to", out_dir)
+
 
 def spawn_ranks(args) -> None:
     """One rank per GPU through `python -m torch.distributed.run` (RCCL rendezvous on 127.0.0.1, a free port), with this
@@ -521,7 +558,8 @@ def spawn_ranks(args) -> None:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)  # ~1 s of timed work: long enough for an external utilisation sampler
+    # default: 100 training steps (~1 s of timed work: long enough for an external utilisation sampler); infer_base: 4
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="base_recipe")
     ap.add_argument("--max-tokens", type=int, default=20000)
@@ -544,14 +582,22 @@ def main():
                          "the line's `value` is then NOT the headline (config.name gets a suffix)")
     ap.add_argument("--timeline", default=None, help="write the per-dispatch timeline (stream, start, duration on the GPU "
                     "clock) of ONE replayed step to this file; tools/timeline.py summarises it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (training: logging output, gradient "
+                         "norm, learning rate, forward outputs, parameters after the update; infer_base: the last batch's "
+                         "hypotheses) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (seeded samples of large arrays)")
     ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_leg:
         return infer_cpu_leg(args) if args.cpu_leg.startswith("infer:") else cpu_leg(args)
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.config == "infer_base":
-        if args.steps == 100:
+        if args.steps is None:
             args.steps = 4  # (default: four passes over the corpus' batch(es))
         return infer_main(args)
+    if args.steps is None:
+        args.steps = 100
 
     if args.exchange_proxy:
         if args.gpus != 1 or "WORLD_SIZE" in os.environ:
@@ -681,7 +727,7 @@ def main():
     t0 = time.perf_counter()
     step_ev = []
     for i in range(args.warmup, args.warmup + args.steps):
-        step(i)
+        last_r = step(i)
         # per-step GPU time (one event record per step end: no synchronisation, not part of the metric) -- the straggler
         # statistic below is simulated from these
         e_ = torch.cuda.Event(enable_timing=True)
@@ -695,6 +741,17 @@ def main():
     dt = time.perf_counter() - t0
     my_dt_local = dt
     vlog('timed region', dt, 'host issue time', t_issue)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed train_step holds -- before any leg below steps the model again
+        trainer.wait_optimizer()
+        arrays = {"log_" + k: torch.tensor([float(v)], dtype=torch.float64) for k, v in last_r["logs"][0].items()}
+        arrays["gnorm"] = last_r["gnorm"].double()
+        arrays["lr"] = torch.tensor([last_r["lr"]], dtype=torch.float64)
+        for k, v in (trainer.criterion.last_outputs or {}).items():
+            if torch.is_tensor(v) and v.is_floating_point():
+                arrays["out_" + k] = v
+        arrays["params_after_update"] = eng.params
+        dump_outputs(args.dump_outputs, arrays)
     last_loss = float(trainer.criterion.last_outputs["stats"][16])  # (of the last TIMED step: the legs below run more)
     # N > 1: what the gradient exchange cost beyond what the backward hid (the compute stream's wait in
     # GradReducer.finish(), GPU clock), and the ranges it was issued in

@@ -11,6 +11,10 @@
     s.dwf = alloc(n, tr);
     bf16raw* wfh = fm ? alloc_h((n + 7) / 8 * 8) : nullptr;
     bf16raw* wdh = fm && need_wd ? alloc_h((n + 7) / 8 * 8) : nullptr;
+    // the permute reads the weights before conv() announces them (touch): on the data-path stream it first waits for the
+    // chunks of an overlapped optimizer update that write them (the second stream is ordered behind the update itself;
+    // the backward's segment watermark is left to conv())
+    if (live() && adam_pending && st_ != side_) adam_wait_upto(p.w + n);
     if (live()) chk(s2st_conv_w_permute(P + p.w, s.wf, s.wd, p.O, p.I, p.Kw, st_, wfh, wdh));
     s.wfh = wfh;
     s.wdh = wdh;

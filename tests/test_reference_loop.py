@@ -4,19 +4,20 @@ plugin's task / model / criterion -- emulator backend, build container -- agains
 under the SAME driver.  Proves what INTEGRATION.md claims: gradients arrive in `p.grad` (views of the gradient arena) also
 after fairseq's `zero_grad()` has set them to None, gradient accumulation over micro-batches adds, the optimizer's in-place
 parameter writes reach the next forward (the bf16 / device copies follow the parameters' version), and the criterion's
-logging output carries the reference's keys."""
+logging output carries the reference's keys.
+
+The reference side is stored in tests/golden/ref_loop.npz (oracle/gen_golden_ref_loop.py): losses, gradient norms and logging
+outputs, and per parameter tensor max |p_ref| and max |p_ref - p_oracle|.  The child recomputes the oracle's parameters, so the
+parameter check uses an upper bound of max |p_ours - p_ref|.  The plugin side runs under fairseq's own classes where fairseq is
+importable, under their restatement in the oracle elsewhere (tests/ref_loop_child.py)."""
 import json
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (build container only)")
 def test_reference_train_step_and_adam_drive_the_plugin():
     subprocess.check_call([os.path.join(ROOT, "tests", "hipemu", "build_emu.sh")], stdout=subprocess.DEVNULL)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ref_loop_child.py"), ROOT], capture_output=True, text=True,
