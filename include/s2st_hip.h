@@ -635,6 +635,31 @@ int64_t s2st_hubert_workspace_floats(s2st_engine* e, int32_t B, int32_t N);
 int s2st_hubert_forward(s2st_engine* e, const float* wave, const int32_t* frame_lens, int32_t B, int32_t N,
                         float* out, float* workspace, int64_t workspace_floats, void* stream);
 
+/* ---- HiFi-GAN generator (--vocoder hifigan): fairseq/models/text_to_speech/hifigan.py:109-162 (Generator:
+ * conv_pre, leaky_relu -> ups[i] -> the multi-receptive-field sum of ResBlocks :20-104, leaky_relu(0.01) -> conv_post ->
+ * tanh) behind vocoder.py:161-186 (HiFiGANVocoder.forward).  The handle is an s2st_engine in "hifigan mode": parameters
+ * are enumerated / bound with s2st_engine_param_info, s2st_engine_bind(params, NULL, NULL) and s2st_engine_bind_bf16
+ * under the reference's state_dict names (".weight" = the weight-norm-folded weight).  Conv weights are stored
+ * [C_out][k][C_in]; ups.<i>.weight in polyphase form [u][C_out][ceil(k/u)][C_in]: phase r, tap n holds the reference's
+ * weight[:, :, j] with j = (r + p) % u + (ceil(k/u) - 1 - n) u (p = (k - u) / 2), zero where j >= k.  Forward only. */
+typedef struct {
+  int32_t in_dim;                 /* 80 */
+  int32_t initial_channel;        /* upsample_initial_channel */
+  int32_t n_ups;                  /* <= 8 */
+  int32_t up_rates[8], up_kernels[8];
+  int32_t n_kernels;              /* <= 4 */
+  int32_t rb_kernels[4], rb_dilations[4][3];
+  int32_t precise;                /* 1: bf16x3 products (fp32 images), 0: bf16 operands */
+} s2st_hifigan_config;
+int s2st_hifigan_create(const s2st_hifigan_config* cfg, s2st_engine** out);
+/* samples produced from T mel frames: (T - 1) u - 2 ((k - u) / 2) + k per upsampling layer; 0 for T = 0 */
+int64_t s2st_hifigan_out_samples(const s2st_engine* e, int32_t T);
+int64_t s2st_hifigan_workspace_floats(s2st_engine* e, int32_t B, int32_t T_max);
+/* mel [B][T][in_dim] fp32 (rows >= frames[b] are ignored), frames [B] int32 -> wave_out [B][out_samples(T)] fp32
+ * (samples >= out_samples(frames[b]) are 0): each utterance as the reference computes it alone */
+int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames, int32_t B, int32_t T, float* wave_out,
+                         float* workspace, int64_t workspace_floats, void* stream);
+
 /* ======================================================================================
  * Gradient exchange: SUM all-reduce over an RCCL communicator, one process per GPU.  Replaces the bucketed NCCL
  * all-reduce torch DDP runs for the reference (fairseq/models/distributed_fairseq_model.py:58-67); the trainer hands

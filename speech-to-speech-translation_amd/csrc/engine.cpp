@@ -334,6 +334,8 @@ struct s2st_engine {
 
 #include "engine_hubert.h"  // the frozen HuBERT front end (config 4)
 
+#include "engine_hifigan.h"  // the HiFi-GAN vocoder (--vocoder hifigan)
+
 #include "engine_step.h"  // one step
 
 };
@@ -936,6 +938,75 @@ int s2st_hubert_forward(s2st_engine* e, const float* wave, const int32_t* frame_
   e->ph_fresh = false;
   int rc = e->forward_hubert(wave, frame_lens, B, N, out);
   e->tape.clear();  // forward only: the front end is frozen (s2st_transformer.py:245-249)
+  return rc;
+}
+
+
+// ---- HiFi-GAN vocoder ---------------------------------------------------------------------------
+int s2st_hifigan_create(const s2st_hifigan_config* cfg, s2st_engine** out) {
+  if (!cfg || !out || cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_kernels < 1 || cfg->n_kernels > 4) return S2ST_ERR_ARG;
+  if (cfg->in_dim < 8 || cfg->in_dim % 8) return S2ST_ERR_SHAPE;
+  for (int i = 0; i <= cfg->n_ups; ++i) {  // every convolution's input channels: a multiple of 8 (16-byte rows)
+    const int ch = cfg->initial_channel >> i;
+    if (ch < 8 || ch % 8 || (ch << i) != cfg->initial_channel) return S2ST_ERR_SHAPE;
+  }
+  for (int i = 0; i < cfg->n_ups; ++i) {
+    const int u = cfg->up_rates[i], k = cfg->up_kernels[i];
+    if (u < 1 || u > 8 || k < u || (k + u - 1) / u > 64) return S2ST_ERR_SHAPE;
+  }
+  for (int j = 0; j < cfg->n_kernels; ++j) {
+    if (cfg->rb_kernels[j] < 1 || cfg->rb_kernels[j] % 2 == 0) return S2ST_ERR_SHAPE;  // "same" padding needs an odd k
+    for (int l = 0; l < 3; ++l)
+      if (cfg->rb_dilations[j][l] < 1 || (cfg->rb_kernels[j] - 1) * cfg->rb_dilations[j][l] > 64) return S2ST_ERR_SHAPE;
+  }
+  s2st_engine* e = new s2st_engine();
+  e->is_hifigan = true;
+  e->gc = *cfg;
+  e->c = s2st_model_config{};
+  e->c.precise = cfg->precise;
+  e->build_params_hifigan();
+  *out = e;
+  return 0;
+}
+
+int64_t s2st_hifigan_out_samples(const s2st_engine* e, int32_t T) {
+  if (!e || !e->is_hifigan) return S2ST_ERR_ARG;
+  return e->hifigan_samples(T);
+}
+
+int64_t s2st_hifigan_workspace_floats(s2st_engine* e, int32_t B, int32_t T_max) {
+  if (!e || !e->is_hifigan) return S2ST_ERR_ARG;
+  e->reset_call();
+  e->dry = true;
+  e->ws = reinterpret_cast<float*>(0x10000);
+  e->ws_cap = (long)1 << 50;
+  e->st_ = nullptr;
+  int rc = e->forward_hifigan(nullptr, nullptr, B, T_max, nullptr);
+  long peak = e->ws_peak;
+  e->reset_call();
+  e->dry = false;
+  return rc ? (int64_t)rc : (int64_t)peak + 1024;
+}
+
+int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames, int32_t B, int32_t T, float* wave_out,
+                         float* workspace, int64_t workspace_floats, void* stream) {
+  if (!e || !e->is_hifigan || !e->P || !mel || !frames || !wave_out) return S2ST_ERR_ARG;
+  e->reset_call();
+  e->dry = false;
+  e->ws = workspace;
+  e->ws_cap = workspace_floats;
+  e->st_ = (hipStream_t)stream;
+  const bool fm = !e->c.precise;
+  if (fm && !e->PH) return S2ST_ERR_ARG;
+  // frozen weights: the bf16 copy is refreshed unless the caller vouches for it (s2st_engine_bf16_is_fresh)
+  if (fm && !e->ph_fresh) {
+    int rc = s2st_cast_bf16_rows(e->P, e->n_params, e->PH, e->n_params, 1, (int)e->n_params, e->st_);
+    if (rc) return rc;
+  }
+  e->ph_fresh = false;
+  int rc = e->forward_hifigan(mel, frames, B, T, wave_out);
+  if (!rc && e->oom) rc = S2ST_ERR_WORKSPACE;
+  e->tape.clear();
   return rc;
 }
 

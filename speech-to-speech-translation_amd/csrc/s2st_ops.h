@@ -288,6 +288,30 @@ int s2st_posconv_prep(float* x, const int* lens, float* img, uint16_t* imgh, int
                       int Tp, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh
+// ---------------------------------------------------------------------------------------
+// y[b][q up + r][o] = epilogue(bias[o] + sum_{c, j} in[b][q + off[r] + j dil][c] * w[r][o][j][c]) for q < nq; input rows
+// outside [0, len_in(b)) read as zero; output rows at or past len_out(b) are written as zeros.  len(b) = frames[b] * la + lb.
+struct s2st_hifigan_conv_args {
+  const void* in;       // [B][lin][cin]: fp32 when in_f32, else bf16
+  const void* w;        // [up][cout][ntap][cin]: fp32 when precise, else bf16
+  const float* bias;    // [cout]
+  const float* resid;   // optional [B][lout][cout] fp32, added after the bias
+  float* out;           // optional [B][lout][cout] fp32 (the MRF accumulator for mrf > 0)
+  void* img;            // optional [B][lout][cout] leaky_relu(y, slope): fp32 when precise, else bf16
+  const int* frames;    // [B]
+  int B, cin, lin, cout, lout, nq, ntap, dil, up, off[8];
+  int la_in, lb_in, la_out, lb_out;
+  int mrf;              // 0: y; 1: out = y; 2: out += y; 3: out = (out + y) / mrf_div
+  float mrf_div, slope;
+  int in_f32, precise;
+};
+int s2st_hifigan_conv(const s2st_hifigan_conv_args& c, hipStream_t st);
+// wave[b][t] = tanh(bias + conv_k(leaky_relu(x, slope))[b][t]) for t < len(b), 0 after; x [B][L][C] fp32, w [k][C]
+int s2st_hifigan_post(const float* x, const float* w, const float* bias, float* wave, const int* frames, int la, int lb,
+                      int B, int L, int C, int k, float slope, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // inference (infer.hip): incremental-decoding attention, stop / alignment / de-CMVN helpers, Griffin-Lim
 // ---------------------------------------------------------------------------------------
 int s2st_decode_attn(const float* q, long ldq, float* kc, float* vc, long ldk, long kbs, const int* klen,

@@ -54,7 +54,7 @@ def make_parser() -> argparse.ArgumentParser:
     a("--seed", type=int, default=1)
     a("--max-target-positions", type=int, default=None, help="AR steps at most (default: the checkpoint's value)")
     a("--eos-prob-threshold", type=float, default=0.5)
-    a("--vocoder", default="griffin_lim", choices=["griffin_lim"])
+    a("--vocoder", default="griffin_lim", choices=["griffin_lim", "hifigan"])
     a("--spec-bwd-max-iter", type=int, default=8)
     a("--gl-phase-rng", default="numpy", choices=["numpy", "device"],
       help="initial Griffin-Lim phases: numpy's global generator (the reference's draws, vocoder.py:101-102) or the device's "
@@ -158,6 +158,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     margs.eos_prob_threshold = args.eos_prob_threshold
     margs.spec_bwd_max_iter = args.spec_bwd_max_iter
     margs.gl_phase_rng = args.gl_phase_rng
+    margs.vocoder = args.vocoder
     margs.precise_gemm = bool(args.precise_gemm)
     margs.eval_inference = False
     margs.train_subset = None

@@ -46,6 +46,8 @@ class S2ST_TranslationTask(TaskBase):  # fairseq's LegacyFairseqTask when fairse
         a("--eos-prob-threshold", type=float, default=0.5)
         a("--eval-inference", action="store_true")
         a("--use-hubert", type=str, default="false")
+        a("--vocoder", type=str, default="griffin_lim", help="griffin_lim | hifigan (s2s_translation.py:66; hifigan reads "
+                                                              "the data config's `vocoder` entry)")
         a("--input-text", type=str, default="false", help="text-to-speech mode (t2s_transformer): the encoder reads src_text")
         a("--speaker-to-id", type=str, default=None, help="use speaker feature: JSON map speaker name -> id "
                                                        "(s2s_translation.py:71)")
@@ -161,9 +163,14 @@ class S2ST_TranslationTask(TaskBase):  # fairseq's LegacyFairseqTask when fairse
         return int(getattr(self.args, "sample_rate", 24000))
 
     def build_default_vocoder(self):
-        """s2s_translation.py:208-215 -> get_vocoder (fairseq/models/text_to_speech/vocoder.py:147-158): Griffin-Lim
-        from the data config's feature settings."""
-        from ..vocoder import GriffinLimVocoder
+        """s2s_translation.py:208-215 -> get_vocoder (fairseq/models/text_to_speech/vocoder.py:188-197): ``--vocoder``
+        griffin_lim (default) from the data config's feature settings, or hifigan from its ``vocoder`` entry."""
+        from ..vocoder import GriffinLimVocoder, HiFiGANVocoder
+        name = getattr(self.args, "vocoder", None) or "griffin_lim"
+        if name == "hifigan":
+            return HiFiGANVocoder.from_data_cfg(self.args, self.data_cfg, device=self.device)
+        if name != "griffin_lim":
+            raise ValueError("Unknown vocoder")
         if self.data_cfg is not None:
             return GriffinLimVocoder.from_data_cfg(self.args, self.data_cfg, device=self.device)
         # synthetic data (no config.yaml): 80-bin log-mel at 24 kHz, hop 300 / window 1200 / n_fft 2048 -- the feature

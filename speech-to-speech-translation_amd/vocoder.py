@@ -622,3 +622,4 @@ class GriffinLimVocoder:
                    window_fn=getattr(torch, feat_cfg["window_fn"] + "_window"),
                    spec_bwd_max_iter=getattr(args, "spec_bwd_max_iter", 32), device=device,
                    phase_rng=getattr(args, "gl_phase_rng", "numpy") or "numpy", seed=int(getattr(args, "seed", 1) or 1))
+from .models.hifigan import HiFiGANVocoder  # noqa: E402,F401  (--vocoder hifigan)
