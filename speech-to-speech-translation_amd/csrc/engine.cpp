@@ -340,6 +340,43 @@ struct s2st_engine {
 
 };
 
+namespace {
+// The workspace a call needs: `body` runs in dry mode (sizes every allocation, launches nothing) on a workspace that is
+// never dereferenced; the peak plus a margin, or the body's error.
+template <class F>
+int64_t dry_run_floats(s2st_engine* e, F body) {
+  e->reset_call();
+  e->dry = true;
+  e->ws = reinterpret_cast<float*>(0x10000);
+  e->ws_cap = (long)1 << 50;
+  e->st_ = nullptr;
+  const int rc = body();
+  const long peak = e->ws_peak;
+  e->reset_call();
+  e->dry = false;
+  return rc ? (int64_t)rc : (int64_t)peak + 1024;
+}
+
+// The forward-only aux decoder paths run on the call's stream alone: the second stream is hidden for the scope.
+struct SingleStream {
+  s2st_engine* e;
+  hipStream_t side;
+  explicit SingleStream(s2st_engine* e_) : e(e_), side(e_->side_) { e->side_ = nullptr; }
+  ~SingleStream() { e->side_ = side; }
+};
+
+s2st_batch eval_batch(int B, int E, const int32_t* enc_lens) {
+  s2st_batch b{};
+  b.B = B; b.E = E; b.training = 0;
+  b.enc_lens = enc_lens;
+  return b;
+}
+
+bool aux_args_ok(const s2st_engine* e, int which) {
+  return e && which >= 0 && which <= 1 && !((which == 0 && !e->c.has_asr) || (which == 1 && !e->c.has_st));
+}
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -505,37 +542,26 @@ int s2st_engine_bind_bf16_transposed(s2st_engine* e, uint16_t* params_bf16_t) {
 }
 
 int64_t s2st_engine_workspace_floats(s2st_engine* e, const s2st_batch* b) {
-  e->reset_call();
-  e->bt = *b;
-  memset(&e->outs, 0, sizeof(e->outs));
-  e->dry = true;
-  e->ws = reinterpret_cast<float*>(0x10000);  // never dereferenced: dry mode launches nothing
-  e->ws_cap = (long)1 << 50;
-  e->st_ = nullptr;
-  // outputs the caller may keep internal are counted as workspace
-  int rc = e->forward();
-  if (rc == 0) {
-    e->gscale = 1.f;
-    for (int s = 0; s < e->n_segments(); ++s) e->backward_segment(s);
-  }
-  long peak = e->ws_peak;
-  e->reset_call();
-  e->dry = false;
-  return rc ? (int64_t)rc : (int64_t)peak + 1024;
+  return dry_run_floats(e, [&] {
+    e->bt = *b;
+    memset(&e->outs, 0, sizeof(e->outs));  // outputs the caller may keep internal are counted as workspace
+    int rc = e->forward();
+    if (rc == 0) {
+      e->gscale = 1.f;
+      for (int s = 0; s < e->n_segments(); ++s) e->backward_segment(s);
+    }
+    return rc;
+  });
 }
 
 int s2st_engine_forward(s2st_engine* e, const s2st_batch* b, const s2st_outputs* out, float* workspace,
                         int64_t workspace_floats, void* stream) {
   if (!e->P || !e->BUF) return S2ST_ERR_ARG;
-  e->reset_call();
+  e->begin_call(workspace, workspace_floats, stream);
   e->bt = *b;
   e->outs = *out;
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
   if (!e->outs.stats && b->tgt) return S2ST_ERR_ARG;
-  return e->forward();
+  return e->forward();  // (the tape stays for the backward)
 }
 
 int s2st_engine_backward(s2st_engine* e, float gscale, int32_t segment, void* stream) {
@@ -596,15 +622,11 @@ int s2st_engine_decode_begin(s2st_engine* e, const s2st_batch* b, const s2st_out
   if (!e->P || !e->BUF || !state || !b || !out) return S2ST_ERR_ARG;
   if (state_floats < s2st_engine_decode_state_floats(e, b->B, b->E, max_steps)) return S2ST_ERR_WORKSPACE;
   e->dec_row_map = nullptr;
-  e->reset_call();
+  e->begin_call(workspace, workspace_floats, stream);
   e->bt = *b;
   e->bt.training = 0;
   e->bt.tgt = nullptr;
   e->outs = *out;
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
   e->stop_after_encoder = true;
   int rc = e->forward();
   e->stop_after_encoder = false;
@@ -629,8 +651,7 @@ int s2st_engine_decode_begin(s2st_engine* e, const s2st_batch* b, const s2st_out
     const XAttnP& xa = e->dec[l].xa;
     e->linear(e->enc_out_keep, xa.kv_w, xa.kv_b, 2 * e->c.dec_dim, e->c.enc_dim, 0, 0.f, nullptr, e->dec_crossKV(l));
   }
-  e->tape.clear();
-  return e->err;
+  return e->end_call(0);
 }
 
 // Several batches decoded as ONE (round 6): the always-on Prenet dropout (tacotron2.py:95-98) keys its mask by the row of the
@@ -646,22 +667,9 @@ int s2st_engine_decode_step(s2st_engine* e, int32_t step, const float* prev, con
                             const int32_t* self_klen, uint64_t seed, float* feat_out, float* eos_prob,
                             float* attn_out, float* workspace, int64_t workspace_floats, void* stream) {
   if (!e->P || !prev || !pos || !feat_out || !eos_prob) return S2ST_ERR_ARG;
-  s2st_engine::Dec keep = e->dec_st;
-  s2st_batch bt_keep = e->bt;
-  e->reset_call();
-  e->dec_st = keep;
-  e->bt = bt_keep;
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
-  e->skws = nullptr; e->skws_n = 0; e->skws_side = nullptr;
-  if (e->fast()) {
-    if (!e->PH) return S2ST_ERR_ARG;  // PH was refreshed by decode_begin's forward
-  }
-  int rc = e->decode_step(step, prev, pos, self_klen, seed, feat_out, eos_prob, attn_out);
-  e->tape.clear();
-  return rc;
+  e->begin_call(workspace, workspace_floats, stream);
+  if (int rc = e->params_ready(false, false)) return rc;  // PH was refreshed by decode_begin's forward
+  return e->end_call(e->decode_step(step, prev, pos, self_klen, seed, feat_out, eos_prob, attn_out));
 }
 
 // ---- the decode step in its graph-replayable form (include/s2st_hip.h: s2st_decode_replay) --------------------------------
@@ -685,22 +693,13 @@ int s2st_engine_decode_step_replay(s2st_engine* e, const s2st_decode_replay* r, 
                                    int64_t workspace_floats, void* stream) {
   if (!e || !e->P || !r || !r->step || !r->seeds || !r->cur_feat || !r->cur_eos || !r->pe_cur) return S2ST_ERR_ARG;
   if (!e->fast() || !e->PH || !e->dec_st.pe_alpha) return S2ST_ERR_SHAPE;
-  s2st_engine::Dec keep = e->dec_st;
-  s2st_batch bt_keep = e->bt;
-  e->reset_call();
-  e->dec_st = keep;
-  e->bt = bt_keep;
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
-  e->skws = nullptr; e->skws_n = 0; e->skws_side = nullptr;
+  e->begin_call(workspace, workspace_floats, stream);
+  if (int rc = e->params_ready(false, false)) return rc;
   e->replay_ = r;
   // (step 0 / seed 0 on the host side: every step-dependent value comes from *r inside the kernels)
   int rc = e->decode_step(0, r->cur_feat, nullptr, self_klen, 0, r->cur_feat, r->cur_eos, r->cur_attn);
   e->replay_ = nullptr;
-  e->tape.clear();
-  return rc;
+  return e->end_call(rc);
 }
 
 int s2st_engine_decode_replay_commit(s2st_engine* e, const s2st_decode_replay* r, uint64_t seed0, float thr, int32_t max_iter,
@@ -715,27 +714,15 @@ int s2st_engine_decode_replay_commit(s2st_engine* e, const s2st_decode_replay* r
 int s2st_engine_postnet_eval(s2st_engine* e, const float* feat, int32_t B, int32_t D, float* post_out,
                              float* workspace, int64_t workspace_floats, void* stream) {
   if (!e->P || !e->BUF || !feat || !post_out) return S2ST_ERR_ARG;
-  s2st_engine::Dec keep = e->dec_st;
-  e->reset_call();
-  e->dec_st = keep;
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
+  e->begin_call(workspace, workspace_floats, stream);
   e->bt.training = 0;
-  e->skws = nullptr; e->skws_n = 0; e->skws_side = nullptr;
-  if (e->fast()) {
-    if (!e->PH) return S2ST_ERR_ARG;
-    int rc = s2st_cast_bf16_rows(e->P, e->n_params, e->PH, e->n_params, 1, (int)e->n_params, e->st_);
-    if (rc) return rc;
-  }
+  if (int rc = e->params_ready()) return rc;
   std::vector<s2st_engine::ConvW> csp;
   for (auto& pc : e->post_conv) csp.push_back(e->make_conv_scratch(pc, false, false));
   Ten* f = e->newT(B * D, e->c.out_dim, const_cast<float*>(feat));
   f->needs_grad = false;
   e->postnet(f, B, D, false, csp, post_out);
-  e->tape.clear();
-  return e->err;
+  return e->end_call(0);
 }
 
 // ---- aux ASR / ST text decoder, forward only (beam search over an aux head: generate_for_s2st.py:107-111) -----
@@ -743,59 +730,29 @@ int s2st_engine_aux_decode(s2st_engine* e, int32_t which, const float* tap, cons
                            const int64_t* prev_tokens, const int32_t* positions, const int32_t* lens, const float* pe,
                            int32_t Bb, int32_t L, int32_t E, float* logits_out, float* workspace,
                            int64_t workspace_floats, void* stream) {
-  if (!e || !e->P || !tap || !enc_lens || !prev_tokens || !positions || !lens || !pe || !logits_out) return S2ST_ERR_ARG;
-  if ((which == 0 && !e->c.has_asr) || (which == 1 && !e->c.has_st) || which < 0 || which > 1) return S2ST_ERR_ARG;
+  if (!aux_args_ok(e, which) || !e->P || !tap || !enc_lens || !prev_tokens || !positions || !lens || !pe || !logits_out)
+    return S2ST_ERR_ARG;
   if (Bb <= 0 || L <= 0 || E <= 0) return S2ST_ERR_SHAPE;
   if (!workspace) return S2ST_ERR_WORKSPACE;
-  e->reset_call();
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
-  e->bt = s2st_batch{};
-  e->bt.B = Bb; e->bt.E = E; e->bt.training = 0;
-  e->bt.enc_lens = enc_lens;
-  e->skws = nullptr; e->skws_n = 0; e->skws_side = nullptr;
-  if (e->fast()) {
-    if (!e->PH) return S2ST_ERR_ARG;
-    int rc = s2st_cast_bf16_rows(e->P, e->n_params, e->PH, e->n_params, 1, (int)e->n_params, e->st_);
-    if (rc) return rc;
-  }
-  hipStream_t keep_side = e->side_;
-  e->side_ = nullptr;  // forward only, one stream
+  e->begin_call(workspace, workspace_floats, stream);
+  e->bt = eval_batch(Bb, E, enc_lens);
+  if (int rc = e->params_ready()) return rc;
+  SingleStream one(e);
   Ten* t = e->newT(Bb * E, e->c.enc_dim, const_cast<float*>(tap));
   t->needs_grad = false;
   e->aux_decoder(which == 0 ? e->asr : e->st, t, (const long*)prev_tokens, positions, lens, Bb, L, pe, logits_out);
-  e->side_ = keep_side;
-  e->tape.clear();
-  return e->err;
+  return e->end_call(0);
 }
 
 // ---- the same decoder step by step with key / value caches (include/s2st_hip.h) --------------------------------------------
-namespace {
-bool aux_inc_args_ok(const s2st_engine* e, int which) {
-  return e && which >= 0 && which <= 1 && !((which == 0 && !e->c.has_asr) || (which == 1 && !e->c.has_st));
-}
-void aux_inc_enter(s2st_engine* e, float* workspace, int64_t workspace_floats, void* stream, int Bb, int E) {
-  e->reset_call();
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
-  e->bt = s2st_batch{};
-  e->bt.B = Bb; e->bt.E = E; e->bt.training = 0;
-  e->skws = nullptr; e->skws_n = 0; e->skws_side = nullptr;
-}
-}  // namespace
-
 int64_t s2st_engine_aux_inc_state_floats(const s2st_engine* e, int32_t which, int32_t Bb, int32_t E, int32_t max_len) {
-  if (!aux_inc_args_ok(e, which) || Bb <= 0 || E <= 0 || max_len <= 0) return S2ST_ERR_ARG;
+  if (!aux_args_ok(e, which) || Bb <= 0 || E <= 0 || max_len <= 0) return S2ST_ERR_ARG;
   const AuxP& a = which == 0 ? e->asr : e->st;
   return 2 * s2st_engine::aux_inc_half(a, Bb, max_len) + (long)a.layers * Bb * E * 2 * a.d + 64;
 }
 
 int64_t s2st_engine_aux_inc_workspace(const s2st_engine* e, int32_t which, int32_t Bb, int32_t E) {
-  if (!aux_inc_args_ok(e, which) || Bb <= 0 || E <= 0) return S2ST_ERR_ARG;
+  if (!aux_args_ok(e, which) || Bb <= 0 || E <= 0) return S2ST_ERR_ARG;
   const AuxP& a = which == 0 ? e->asr : e->st;
   // begin: bf16 copies of the tap and of every layer's K | V projection; a step: a few dozen [Bb][width] tensors
   long w = a.in_dim;
@@ -805,72 +762,46 @@ int64_t s2st_engine_aux_inc_workspace(const s2st_engine* e, int32_t which, int32
 
 int s2st_engine_aux_inc_begin(s2st_engine* e, int32_t which, const float* tap, const int32_t* enc_lens, int32_t Bb, int32_t E,
                               int32_t max_len, float* state, float* workspace, int64_t workspace_floats, void* stream) {
-  if (!aux_inc_args_ok(e, which) || !e->P || !tap || !enc_lens || !state) return S2ST_ERR_ARG;
+  if (!aux_args_ok(e, which) || !e->P || !tap || !enc_lens || !state) return S2ST_ERR_ARG;
   if (Bb <= 0 || E <= 0 || max_len <= 0) return S2ST_ERR_SHAPE;
   if (!workspace) return S2ST_ERR_WORKSPACE;
-  aux_inc_enter(e, workspace, workspace_floats, stream, Bb, E);
-  e->bt.enc_lens = enc_lens;
-  if (e->fast()) {
-    if (!e->PH) return S2ST_ERR_ARG;
-    int rc = s2st_cast_bf16_rows(e->P, e->n_params, e->PH, e->n_params, 1, (int)e->n_params, e->st_);
-    if (rc) return rc;
-  }
-  hipStream_t keep_side = e->side_;
-  e->side_ = nullptr;  // forward only, one stream
+  e->begin_call(workspace, workspace_floats, stream);
+  e->bt = eval_batch(Bb, E, enc_lens);
+  if (int rc = e->params_ready()) return rc;
+  SingleStream one(e);
   s2st_engine::AuxInc& S = e->aux_inc[which];
   S = s2st_engine::AuxInc{};
   S.base = state; S.Bb = Bb; S.E = E; S.maxT = max_len; S.enc_lens = enc_lens;
   Ten* t = e->newT(Bb * E, e->c.enc_dim, const_cast<float*>(tap));
   t->needs_grad = false;
-  const int rc = e->aux_inc_begin(which == 0 ? e->asr : e->st, S, t);
-  e->side_ = keep_side;
-  e->tape.clear();
-  return rc;
+  return e->end_call(e->aux_inc_begin(which == 0 ? e->asr : e->st, S, t));
 }
 
 int s2st_engine_aux_inc_step(s2st_engine* e, int32_t which, int32_t step, const int64_t* tokens, const int32_t* reorder,
                              const int32_t* positions, const float* pe, float* logits_out, float* workspace,
                              int64_t workspace_floats, void* stream) {
-  if (!aux_inc_args_ok(e, which) || !e->P || !tokens || !positions || !pe || !logits_out) return S2ST_ERR_ARG;
+  if (!aux_args_ok(e, which) || !e->P || !tokens || !positions || !pe || !logits_out) return S2ST_ERR_ARG;
   if (!workspace) return S2ST_ERR_WORKSPACE;
-  s2st_engine::AuxInc keep = e->aux_inc[which];
-  if (!keep.base) return S2ST_ERR_ARG;
-  s2st_engine::AuxInc keep_other = e->aux_inc[1 - which];
-  aux_inc_enter(e, workspace, workspace_floats, stream, keep.Bb, keep.E);
-  e->aux_inc[which] = keep;
-  e->aux_inc[1 - which] = keep_other;
-  e->bt.enc_lens = keep.enc_lens;
-  if (e->fast() && !e->PH) return S2ST_ERR_ARG;  // (PH was refreshed by aux_inc_begin)
-  hipStream_t keep_side = e->side_;
-  e->side_ = nullptr;
-  const int rc = e->aux_inc_step(which == 0 ? e->asr : e->st, e->aux_inc[which], step, (const long*)tokens, reorder, positions, pe,
-                                 logits_out);
-  e->side_ = keep_side;
-  e->tape.clear();
-  return rc;
+  s2st_engine::AuxInc& S = e->aux_inc[which];
+  if (!S.base) return S2ST_ERR_ARG;
+  e->begin_call(workspace, workspace_floats, stream);
+  e->bt = eval_batch(S.Bb, S.E, S.enc_lens);
+  if (int rc = e->params_ready(false, false)) return rc;  // (PH was refreshed by aux_inc_begin)
+  SingleStream one(e);
+  return e->end_call(e->aux_inc_step(which == 0 ? e->asr : e->st, S, step, (const long*)tokens, reorder, positions, pe,
+                                     logits_out));
 }
 
 int64_t s2st_engine_aux_decode_workspace(s2st_engine* e, int32_t which, int32_t Bb, int32_t L, int32_t E) {
-  if (!e || which < 0 || which > 1 || (which == 0 && !e->c.has_asr) || (which == 1 && !e->c.has_st)) return S2ST_ERR_ARG;
-  e->reset_call();
-  e->dry = true;
-  e->ws = reinterpret_cast<float*>(0x10000);
-  e->ws_cap = (long)1 << 50;
-  e->st_ = nullptr;
-  e->bt = s2st_batch{};
-  e->bt.B = Bb; e->bt.E = E; e->bt.training = 0;
-  e->skws = nullptr; e->skws_n = 0; e->skws_side = nullptr;
-  hipStream_t keep_side = e->side_;
-  e->side_ = nullptr;
-  Ten* t = e->newT(Bb * E, e->c.enc_dim, reinterpret_cast<float*>(0x10000));
-  t->needs_grad = false;
-  e->aux_decoder(which == 0 ? e->asr : e->st, t, nullptr, nullptr, nullptr, Bb, L, nullptr, reinterpret_cast<float*>(0x10000));
-  e->side_ = keep_side;
-  const long peak = e->ws_peak;
-  const int err = e->err;
-  e->reset_call();
-  e->dry = false;
-  return err ? (int64_t)err : (int64_t)peak + 1024;
+  if (!aux_args_ok(e, which)) return S2ST_ERR_ARG;
+  return dry_run_floats(e, [&] {
+    e->bt = eval_batch(Bb, E, nullptr);
+    SingleStream one(e);
+    Ten* t = e->newT(Bb * E, e->c.enc_dim, e->ws);  // (tap and logits: the dry workspace, never dereferenced)
+    t->needs_grad = false;
+    e->aux_decoder(which == 0 ? e->asr : e->st, t, nullptr, nullptr, nullptr, Bb, L, nullptr, e->ws);
+    return e->err;
+  });
 }
 
 // ---- HuBERT front end ---------------------------------------------------------------------------
@@ -907,38 +838,17 @@ int32_t s2st_hubert_out_frames(const s2st_engine* e, int32_t n_samples) { return
 
 int64_t s2st_hubert_workspace_floats(s2st_engine* e, int32_t B, int32_t N) {
   if (!e->is_hubert) return S2ST_ERR_ARG;
-  e->reset_call();
-  e->dry = true;
-  e->ws = reinterpret_cast<float*>(0x10000);
-  e->ws_cap = (long)1 << 50;
-  e->st_ = nullptr;
-  int rc = e->forward_hubert(nullptr, nullptr, B, N, nullptr);
-  long peak = e->ws_peak;
-  e->reset_call();
-  e->dry = false;
-  return rc ? (int64_t)rc : (int64_t)peak + 1024;
+  return dry_run_floats(e, [&] { return e->forward_hubert(nullptr, nullptr, B, N, nullptr); });
 }
 
 int s2st_hubert_forward(s2st_engine* e, const float* wave, const int32_t* frame_lens, int32_t B, int32_t N, float* out,
                         float* workspace, int64_t workspace_floats, void* stream) {
   if (!e->is_hubert || !e->P || !wave || !frame_lens || !out) return S2ST_ERR_ARG;
-  e->reset_call();
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
-  const bool fm = e->fast();
-  if (fm && !e->PH) return S2ST_ERR_ARG;
-  // frozen weights: the bf16 copy is refreshed unless the caller vouches for it (s2st_engine_bf16_is_fresh before this call:
-  // the host side tracks the parameter tensor's version -- 0.1 ms of the 6.9 ms forward)
-  if (fm && !e->ph_fresh) {
-    int rc = s2st_cast_bf16_rows(e->P, e->n_params, e->PH, e->n_params, 1, (int)e->n_params, e->st_);
-    if (rc) return rc;
-  }
-  e->ph_fresh = false;
-  int rc = e->forward_hubert(wave, frame_lens, B, N, out);
-  e->tape.clear();  // forward only: the front end is frozen (s2st_transformer.py:245-249)
-  return rc;
+  e->begin_call(workspace, workspace_floats, stream);
+  // frozen weights: the host side tracks the parameter tensor's version and vouches for the bf16 copy (0.1 ms of the
+  // 6.9 ms forward); forward only: the front end is frozen (s2st_transformer.py:245-249)
+  if (int rc = e->params_ready()) return rc;
+  return e->end_call(e->forward_hubert(wave, frame_lens, B, N, out));
 }
 
 
@@ -976,38 +886,15 @@ int64_t s2st_hifigan_out_samples(const s2st_engine* e, int32_t T) {
 
 int64_t s2st_hifigan_workspace_floats(s2st_engine* e, int32_t B, int32_t T_max) {
   if (!e || !e->is_hifigan) return S2ST_ERR_ARG;
-  e->reset_call();
-  e->dry = true;
-  e->ws = reinterpret_cast<float*>(0x10000);
-  e->ws_cap = (long)1 << 50;
-  e->st_ = nullptr;
-  int rc = e->forward_hifigan(nullptr, nullptr, B, T_max, nullptr);
-  long peak = e->ws_peak;
-  e->reset_call();
-  e->dry = false;
-  return rc ? (int64_t)rc : (int64_t)peak + 1024;
+  return dry_run_floats(e, [&] { return e->forward_hifigan(nullptr, nullptr, B, T_max, nullptr); });
 }
 
 int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames, int32_t B, int32_t T, float* wave_out,
                          float* workspace, int64_t workspace_floats, void* stream) {
   if (!e || !e->is_hifigan || !e->P || !mel || !frames || !wave_out) return S2ST_ERR_ARG;
-  e->reset_call();
-  e->dry = false;
-  e->ws = workspace;
-  e->ws_cap = workspace_floats;
-  e->st_ = (hipStream_t)stream;
-  const bool fm = !e->c.precise;
-  if (fm && !e->PH) return S2ST_ERR_ARG;
-  // frozen weights: the bf16 copy is refreshed unless the caller vouches for it (s2st_engine_bf16_is_fresh)
-  if (fm && !e->ph_fresh) {
-    int rc = s2st_cast_bf16_rows(e->P, e->n_params, e->PH, e->n_params, 1, (int)e->n_params, e->st_);
-    if (rc) return rc;
-  }
-  e->ph_fresh = false;
-  int rc = e->forward_hifigan(mel, frames, B, T, wave_out);
-  if (!rc && e->oom) rc = S2ST_ERR_WORKSPACE;
-  e->tape.clear();
-  return rc;
+  e->begin_call(workspace, workspace_floats, stream);
+  if (int rc = e->params_ready()) return rc;  // (frozen weights, as in s2st_hubert_forward)
+  return e->end_call(e->forward_hifigan(mel, frames, B, T, wave_out));
 }
 
 }  // extern "C"

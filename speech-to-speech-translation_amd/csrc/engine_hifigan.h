@@ -69,7 +69,6 @@
 
   int forward_hifigan(const float* mel, const int* frames, int B, int T, float* wave) {
     const bool pr = c.precise != 0;
-    if (!pr && !PH && !dry) return S2ST_ERR_ARG;
     if (B <= 0 || T <= 0) return S2ST_ERR_SHAPE;
     bt = s2st_batch{};
     bt.B = B;

@@ -40,12 +40,10 @@
 
   int forward_hubert(const float* wave, const int* frame_lens, int B, int N, float* out) {
     const bool fm = fast();
-    if (fm && !PH && !dry) return S2ST_ERR_ARG;
     bt = s2st_batch{};
     bt.B = B;
     bt.training = 0;
     bt.enc_lens = frame_lens;
-    skws = nullptr; skws_n = 0; skws_side = nullptr;
     // conv0 (1 -> C0) + GroupNorm(C0, C0) over ALL Tn frames of the padded batch + GELU
     const int C0 = hc.conv_dim[0];
     int Tin = (N - hc.conv_k[0]) / hc.conv_stride[0] + 1;

@@ -24,6 +24,36 @@
     site_ctx[0] = 0;
     param_watermark = 0;
     next_segment = 0;
+    skws = nullptr; skws_n = 0; skws_side = nullptr;  // (forward() allots them; the backward segments reuse them)
+  }
+  // prologue of every call that launches work: a fresh call on `stream` with the caller's workspace
+  void begin_call(float* workspace, long workspace_floats, void* stream) {
+    reset_call();
+    dry = false;
+    ws = workspace;
+    ws_cap = workspace_floats;
+    st_ = (hipStream_t)stream;
+  }
+  // The one place that decides whether this call may read the parameters: P once a pending overlapped update has landed
+  // on st_; in fast mode PH too, cast from P here unless the caller vouched for it (s2st_engine_bf16_is_fresh).
+  // chunked: the caller waits for the update chunk by chunk as it reads (touch(): forward), so the whole-arena wait is
+  //   needed only before the cast -- when the update itself wrote PH, it is skipped.
+  // refresh = false: a step of a run whose begin call made PH (decode / incremental aux steps): no cast, ph_fresh kept.
+  int params_ready(bool chunked = false, bool refresh = true) {
+    if (dry) return 0;
+    const bool fm = fast();
+    if (fm && !PH) return S2ST_ERR_ARG;
+    if (adam_pending && !(chunked && fm && ph_fresh)) adam_wait_all(st_);
+    if (fm && refresh) {
+      if (!ph_fresh) chk(s2st_cast_bf16_rows(P, n_params, PH, n_params, 1, (int)n_params, st_));
+      ph_fresh = false;
+    }
+    return err;
+  }
+  // epilogue of every call that leaves nothing for a backward: the tape goes, the first error is returned
+  int end_call(int rc) {
+    tape.clear();
+    return rc ? rc : err;
   }
 
   int forward() {
@@ -47,13 +77,8 @@
     // scratch at the bottom of the workspace
     const float *pe_enc = bt.pe_enc, *pe_dec = bt.pe_dec, *pe_asr = bt.pe_asr, *pe_st = bt.pe_st;
     const bool fm = fast();
-    if (fm && !PH && !dry) return S2ST_ERR_ARG;
     // bf16 copy of the whole parameter arena (292 MB read + 146 MB written: ~0.08 ms)
-    if (adam_pending && live() && (!fm || !ph_fresh)) adam_wait_all(st_);  // the whole arena is read right away
-    if (fm && live()) {
-      if (!ph_fresh) chk(s2st_cast_bf16_rows(P, n_params, PH, n_params, 1, (int)n_params, st_));
-      ph_fresh = false;
-    }
+    if (int rc = params_ready(true)) return rc;
     // transposed weight copies for the backward, made on the second stream (idle during the forward)
     pht_valid = false;
     if (fm && tr && PHT && live()) {

@@ -142,8 +142,6 @@ def batch_by_size(
     assert len(ntok) == n
     ends = np.zeros(n + 1, dtype=np.int32)
     fn = bd.lib().s2st_batch_by_size
-    fn.restype = C.c_int64
-    fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
     count = fn(ntok.ctypes.data, n, int(max_tokens), int(max_sentences), int(bsz_mult), ends.ctypes.data)
     if count == -2 or (max_tokens > 0 and int(ntok.max()) > max_tokens):
         raise AssertionError(f"Sentences lengths should not exceed max_tokens={max_tokens}")

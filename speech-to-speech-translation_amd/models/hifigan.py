@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from ..runtime import binding as bd
-from ..runtime.engine import ParamInfo
+from ..runtime.frozen import FrozenNet
 
 
 class HiFiGANConfigC(C.Structure):
@@ -47,13 +47,14 @@ def _polyphase(w: torch.Tensor, u: int) -> torch.Tensor:
     return out
 
 
-class HiFiGANVocoder:
+class HiFiGANVocoder(FrozenNet):
     """``HiFiGANVocoder(checkpoint_path, model_cfg)`` as the reference's; ``precise=True`` selects the bf16x3 products
     (``--precise-gemm``), otherwise bf16 operands with fp32 accumulation."""
+    kind = "hifigan"
 
     def __init__(self, checkpoint_path: Optional[str], model_cfg: Dict, fp16: bool = False, device=None,
                  precise: bool = False, state_dict: Optional[Dict[str, torch.Tensor]] = None):
-        self.device = torch.device(device) if device is not None else (
+        device = torch.device(device) if device is not None else (
             torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
         self.cfg = dict(model_cfg)
         self.precise = bool(precise)
@@ -64,7 +65,6 @@ class HiFiGANVocoder:
         self.in_dim = int(self.cfg.get("model_in_dim", 80))
         if len(self.rb_kernels) != len(self.rb_dil) or any(len(d) != 3 for d in self.rb_dil):
             raise ValueError("resblock_kernel_sizes / resblock_dilation_sizes: one triple of dilations per kernel")
-        lib = self.lib = bd.lib()
         cfg = HiFiGANConfigC()
         cfg.in_dim, cfg.initial_channel, cfg.n_ups = self.in_dim, self.c0, len(self.ups)
         for i, (u, k) in enumerate(self.ups):
@@ -75,54 +75,11 @@ class HiFiGANVocoder:
             for l in range(3):
                 cfg.rb_dilations[j][l] = int(self.rb_dil[j][l])
         cfg.precise = int(self.precise)
-        lib.s2st_hifigan_create.argtypes = [C.POINTER(HiFiGANConfigC), C.POINTER(C.c_void_p)]
-        lib.s2st_engine_destroy.argtypes = [C.c_void_p]
-        lib.s2st_engine_destroy.restype = None
-        lib.s2st_engine_num_params.argtypes = [C.c_void_p]
-        lib.s2st_engine_param_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ParamInfo)]
-        lib.s2st_engine_param_floats.argtypes = [C.c_void_p]
-        lib.s2st_engine_param_floats.restype = C.c_int64
-        lib.s2st_engine_bind.argtypes = [C.c_void_p] * 4
-        lib.s2st_engine_bind_bf16.argtypes = [C.c_void_p, C.c_void_p]
-        lib.s2st_engine_bf16_is_fresh.argtypes = [C.c_void_p]
-        lib.s2st_hifigan_out_samples.argtypes = [C.c_void_p, C.c_int32]
-        lib.s2st_hifigan_out_samples.restype = C.c_int64
-        lib.s2st_hifigan_workspace_floats.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.s2st_hifigan_workspace_floats.restype = C.c_int64
-        lib.s2st_hifigan_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                             C.c_void_p, C.c_int64, C.c_void_p]
-        h = C.c_void_p()
-        bd.check(lib.s2st_hifigan_create(C.byref(cfg), C.byref(h)), "s2st_hifigan_create")
-        self.h = h
-        self.n_params = int(lib.s2st_engine_param_floats(h))
-        self.infos: List[Tuple[str, int, int, Tuple[int, ...]]] = []
-        for i in range(lib.s2st_engine_num_params(h)):
-            pi = ParamInfo()
-            bd.check(lib.s2st_engine_param_info(h, i, C.byref(pi)), "param_info")
-            self.infos.append((pi.name.decode(), int(pi.offset), int(pi.numel), tuple(pi.shape[:pi.ndim])))
-        self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
-        lib.s2st_engine_bind(h, self.params.data_ptr(), None, None)
-        self.params_bf16 = None
-        if not self.precise:
-            self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=self.device)
-            lib.s2st_engine_bind_bf16(h, self.params_bf16.data_ptr())
-        self._ph_version = None
-        self.workspace: Optional[torch.Tensor] = None
+        self._create(device, cfg, self.precise)
         if state_dict is None and checkpoint_path is not None:
             state_dict = torch.load(checkpoint_path, map_location="cpu")["generator"]
         if state_dict is not None:
             self.load_state_dict(state_dict)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.s2st_engine_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def eval(self):
-        return self
 
     def cuda(self):
         return self
@@ -143,12 +100,6 @@ class HiFiGANVocoder:
                    precise=bool(getattr(args, "precise_gemm", False)))
 
     # -- parameters: reference names / layouts -> engine arena ----------------------------------------
-    def _view(self, name):
-        for n, off, numel, shape in self.infos:
-            if n == name:
-                return self.params[off:off + numel].view(shape)
-        raise KeyError(name)
-
     def reference_shapes(self) -> Dict[str, Tuple[int, ...]]:
         """The effective (weight-norm folded) shape of every tensor, in the reference's layout."""
         s: Dict[str, Tuple[int, ...]] = {}
@@ -199,7 +150,7 @@ class HiFiGANVocoder:
             elif n.endswith(".weight"):
                 w = w.permute(0, 2, 1)
             self._view(n).copy_(w.reshape(shape).to(self.device))
-        self._ph_version = None
+        self.invalidate_bf16()
 
     # -- forward ------------------------------------------------------------------------------------------
     def out_samples(self, n_frames: int) -> int:
@@ -214,24 +165,14 @@ class HiFiGANVocoder:
             raise ValueError(f"expected {self.in_dim} mel bins, got {D}")
         if B == 0 or T == 0:
             return torch.zeros(B, self.out_samples(T), device=self.device)
-        n = int(self.lib.s2st_hifigan_workspace_floats(self.h, B, T))
-        if n < 0:
-            raise bd.S2STHipError(f"s2st_hifigan_workspace_floats failed with code {n}")
-        if self.workspace is None or self.workspace.numel() < n:
-            self.workspace = torch.empty(n, dtype=torch.float32, device=self.device)
         if len(frames) != B or any(not 0 <= int(f) <= T for f in frames):
             raise ValueError(f"frames must be {B} lengths in [0, {T}]")
         fr = torch.tensor([int(f) for f in frames], dtype=torch.int32)
         if self.device.type == "cuda":
             fr = fr.pin_memory().to(self.device, non_blocking=True)
         wave = torch.empty(B, self.out_samples(T), dtype=torch.float32, device=self.device)
-        # frozen weights: the engine's bf16 copy stays valid while nobody wrote the parameter tensor
-        if self.params_bf16 is not None and self._ph_version == self.params._version:
-            self.lib.s2st_engine_bf16_is_fresh(self.h)
-        self._ph_version = self.params._version
-        bd.check(self.lib.s2st_hifigan_forward(self.h, mel.data_ptr(), fr.data_ptr(), B, T, wave.data_ptr(),
-                                               self.workspace.data_ptr(), self.workspace.numel(),
-                                               C.c_void_p(bd.stream_ptr())), "s2st_hifigan_forward")
+        self._reserve(B, T)
+        self._forward(mel.data_ptr(), fr.data_ptr(), B, T, wave.data_ptr())
         self._keep = (mel, fr)
         return wave
 

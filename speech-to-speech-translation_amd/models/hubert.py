@@ -14,12 +14,12 @@ frozen).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
 from ..runtime import binding as bd
-from ..runtime.engine import ParamInfo
+from ..runtime.frozen import FrozenNet
 
 BASE_CONV = [(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)] * 2
 
@@ -30,73 +30,25 @@ class HubertConfigC(C.Structure):
                     "embed", "layers", "heads", "ffn", "conv_pos", "conv_pos_groups", "precise")]
 
 
-class HubertFrontend:
+class HubertFrontend(FrozenNet):
     """hubert_base geometry by default (conv stack 7 layers, 12 x 768, 12 heads, ffn 3072, conv_pos 128/16)."""
+    kind = "hubert"
 
     def __init__(self, device: torch.device, conv=None, embed=768, layers=12, heads=12, ffn=3072, conv_pos=128,
                  conv_pos_groups=16, precise: bool = False):
-        self.device = device
         self.conv = list(conv or BASE_CONV)
         self.embed, self.layers, self.heads, self.ffn = embed, layers, heads, ffn
         self.conv_pos, self.groups, self.precise = conv_pos, conv_pos_groups, precise
-        lib = self.lib = bd.lib()
         cfg = HubertConfigC()
         cfg.n_conv = len(self.conv)
         for i, (c, k, s) in enumerate(self.conv):
             cfg.conv_dim[i], cfg.conv_k[i], cfg.conv_stride[i] = c, k, s
         cfg.embed, cfg.layers, cfg.heads, cfg.ffn = embed, layers, heads, ffn
         cfg.conv_pos, cfg.conv_pos_groups, cfg.precise = conv_pos, conv_pos_groups, int(precise)
-        lib.s2st_hubert_create.argtypes = [C.POINTER(HubertConfigC), C.POINTER(C.c_void_p)]
-        lib.s2st_engine_destroy.argtypes = [C.c_void_p]
-        lib.s2st_engine_destroy.restype = None
-        lib.s2st_engine_num_params.argtypes = [C.c_void_p]
-        lib.s2st_engine_param_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ParamInfo)]
-        lib.s2st_engine_param_floats.argtypes = [C.c_void_p]
-        lib.s2st_engine_param_floats.restype = C.c_int64
-        lib.s2st_engine_bind.argtypes = [C.c_void_p] * 4
-        lib.s2st_engine_bind_bf16.argtypes = [C.c_void_p, C.c_void_p]
-        lib.s2st_hubert_out_frames.argtypes = [C.c_void_p, C.c_int32]
-        lib.s2st_hubert_workspace_floats.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.s2st_hubert_workspace_floats.restype = C.c_int64
-        lib.s2st_hubert_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                            C.c_void_p, C.c_int64, C.c_void_p]
-        h = C.c_void_p()
-        bd.check(lib.s2st_hubert_create(C.byref(cfg), C.byref(h)), "s2st_hubert_create")
-        self.h = h
-        self.n_params = int(lib.s2st_engine_param_floats(h))
-        self.infos: List[Tuple[str, int, int, Tuple[int, ...]]] = []
-        for i in range(lib.s2st_engine_num_params(h)):
-            pi = ParamInfo()
-            bd.check(lib.s2st_engine_param_info(h, i, C.byref(pi)), "param_info")
-            self.infos.append((pi.name.decode(), int(pi.offset), int(pi.numel), tuple(pi.shape[:pi.ndim])))
-        self.params = torch.zeros(self.n_params, dtype=torch.float32, device=device)
-        lib.s2st_engine_bind(h, self.params.data_ptr(), None, None)
-        self.params_bf16 = None
-        if not precise:
-            self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device)
-            lib.s2st_engine_bind_bf16(h, self.params_bf16.data_ptr())
-        self.workspace: Optional[torch.Tensor] = None
-        self._plan: Dict[Tuple[int, int], int] = {}
+        self._create(device, cfg, precise)
         self._extra: Dict[str, torch.Tensor] = {}  # reference tensors the forward does not read
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.s2st_engine_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def eval(self):  # the reference calls hubert.eval() every forward (s2st_transformer.py:246)
-        return self
-
     # -- parameters: reference names / layouts <-> engine arena ------------------------------------
-    def _view(self, name):
-        for n, off, numel, shape in self.infos:
-            if n == name:
-                return self.params[off:off + numel].view(shape)
-        raise KeyError(name)
-
     def reference_shapes(self) -> Dict[str, Tuple[int, ...]]:
         s: Dict[str, Tuple[int, ...]] = {}
         for n, _, _, shape in self.infos:
@@ -230,51 +182,14 @@ class HubertFrontend:
         """Device side: the frozen forward of staged inputs into ``out`` [B, T, embed] (no host work besides the
         enqueue: what a training step repeats on a prepared batch)."""
         B, N = wave.shape
-        key = (B, N)
-        if key not in self._plan:
-            n = int(self.lib.s2st_hubert_workspace_floats(self.h, B, N))
-            if n < 0:
-                raise bd.S2STHipError(f"s2st_hubert_workspace_floats failed with code {n}")
-            self._plan[key] = n
-        need = self._plan[key]
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        # frozen weights: the engine's bf16 copy stays valid while nobody wrote the parameter tensor (or a view of it).
-        # torch's version counter sees in-place ops on the tensor and its views; writers that bypass it (``.data``, raw
-        # pointers: a C-side load, broadcast_ on a .data view) call invalidate_bf16().  The cast of the last refresh ran on
-        # ONE stream: a forward on another stream waits for that cast's event before it reads the copy (ADVICE r5).
-        cur = torch.cuda.current_stream() if self.device.type == "cuda" else None
-        if self.params_bf16 is not None and getattr(self, "_ph_version", None) == self.params._version:
-            ev = getattr(self, "_ph_event", None)
-            if ev is not None and cur is not None and getattr(self, "_ph_stream", None) != cur.cuda_stream:
-                cur.wait_event(ev)
-            self.lib.s2st_engine_bf16_is_fresh(self.h)
-            refreshed = False
-        else:
-            refreshed = True
-        self._ph_version = self.params._version
-        bd.check(self.lib.s2st_hubert_forward(self.h, wave.data_ptr(), lens.data_ptr(), B, N, out.data_ptr(),
-                                              self.workspace.data_ptr(), self.workspace.numel(),
-                                              C.c_void_p(bd.stream_ptr())), "s2st_hubert_forward")
-        if refreshed and cur is not None:  # the refresh cast was enqueued by this forward, on this stream
-            self._ph_event = torch.cuda.Event()
-            self._ph_event.record(cur)
-            self._ph_stream = cur.cuda_stream
+        self._reserve(B, N)
+        self._forward(wave.data_ptr(), lens.data_ptr(), B, N, out.data_ptr())
         self._keep = (wave, lens)
         return out
 
-    def invalidate_bf16(self):
-        """The parameters were written behind torch's version counter: the next forward refreshes the bf16 copy."""
-        self._ph_version = None
-
     def reserve(self, B: int, N: int):
         """Size the workspace for a [B, N] waveform batch up front (no allocation inside a training loop)."""
-        n = int(self.lib.s2st_hubert_workspace_floats(self.h, B, N))
-        if n < 0:
-            raise bd.S2STHipError(f"s2st_hubert_workspace_floats failed with code {n}")
-        self._plan[(B, N)] = n
-        if self.workspace is None or self.workspace.numel() < n:
-            self.workspace = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._reserve(B, N)
 
     def extract_features(self, source: torch.Tensor, padding_mask: Optional[torch.Tensor] = None,
                          mask: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -63,8 +63,11 @@ def load_library(path: Optional[str] = None, emulator: bool = False) -> C.CDLL:
             " (hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _lib = C.CDLL(path)
     _lib_is_emulator = emulator
-    _lib.s2st_version.restype = C.c_int
-    _lib.s2st_device_count.restype = C.c_int
+    # every entry point the library exports gets its signature from the header: struct arguments go as C.byref(...)
+    for name, (ret, alist) in header_prototypes().items():
+        fn = getattr(_lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = ret, [t for t, _ in alist]
     return _lib
 
 
@@ -173,9 +176,7 @@ def gemm_args_bf16(A, B, Cout, M, N, K, *, a_kmajor=True, b_kmajor=True, a_ld=No
 def gemm_group(problems):
     """s2st_gemm_group_f32: up to 8 bf16 problems of the same operand layouts in one persistent launch."""
     arr = (GemmArgs * len(problems))(*problems)
-    fn = lib().s2st_gemm_group_f32
-    fn.argtypes = [C.POINTER(GemmArgs), C.c_int32, C.c_void_p]
-    check(fn(arr, len(problems), C.c_void_p(stream_ptr())), "s2st_gemm_group_f32")
+    check(lib().s2st_gemm_group_f32(arr, len(problems), C.c_void_p(stream_ptr())), "s2st_gemm_group_f32")
 
 
 class AttnArgs(C.Structure):
@@ -208,7 +209,6 @@ def flash_attention(q, k, v, H, *, klen=None, causal=False, scale=None, drop_p=0
     a.B, a.H, a.T, a.S, a.dh, a.causal = B, H, T, S, dh, 1 if causal else 0
     a.scale = scale if scale is not None else dh ** -0.5
     a.drop_p, a.seed, a.ld_drop = drop_p, seed, (S + 7) // 8 * 8
-    lib().s2st_flash_attn_fwd_bf16.argtypes = [C.POINTER(AttnArgs), C.c_void_p]
     check(lib().s2st_flash_attn_fwd_bf16(C.byref(a), C.c_void_p(stream_ptr())), "s2st_flash_attn_fwd_bf16")
     if dO is None:
         return o, lse.view(B, H, T)
@@ -223,7 +223,6 @@ def flash_attention(q, k, v, H, *, klen=None, causal=False, scale=None, drop_p=0
                 [torch.zeros(Cm, dtype=torch.float32, device=q.device) for _ in range(3)]
         a.dqh, a.dkh, a.dvh = (t.data_ptr() for t in extra[:3])
         a.dbq, a.dbk, a.dbv = (t.data_ptr() for t in extra[3:])
-    lib().s2st_flash_attn_bwd_bf16.argtypes = [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p, C.c_void_p]
     check(lib().s2st_flash_attn_bwd_bf16(C.byref(a), dO.data_ptr(), scratch.data_ptr(), C.c_void_p(stream_ptr())),
           "s2st_flash_attn_bwd_bf16")
     if extra is not None:
@@ -232,8 +231,8 @@ def flash_attention(q, k, v, H, *, klen=None, causal=False, scale=None, drop_p=0
 
 
 # ---------------------------------------------------------------------------------------------
-# generic call path: argtypes are derived from include/s2st_hip.h so the binding cannot drift
-# from the declared C ABI
+# the signatures of every entry point are derived from include/s2st_hip.h (load_library) so the
+# binding cannot drift from the declared C ABI
 # ---------------------------------------------------------------------------------------------
 import re
 
@@ -251,8 +250,8 @@ def header_prototypes():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     out = {}
-    for m in re.finditer(r"\b(int|int32_t|int64_t|void)\s+(s2st_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+    for m in re.finditer(r"\b(int|int32_t|int64_t|void)(\s*\*\s*|\s+)(s2st_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
+        ret, name, args = m.group(1) + m.group(2).strip(), m.group(3), m.group(4).strip()
         alist = []
         if args and args != "void":
             for a in args.split(","):
@@ -264,20 +263,13 @@ def header_prototypes():
                 else:
                     ty, nm = a.rsplit(" ", 1)
                     alist.append((_CT[ty.replace("const ", "").strip()], nm))
-        out[name] = ({"int64_t": C.c_int64, "void": None}.get(ret, C.c_int), alist)
+        out[name] = ({"int64_t": C.c_int64, "void": None}.get(ret, C.c_void_p if ret.endswith("*") else C.c_int), alist)
     _protos = out
     return out
 
 
 def _bind(name):
-    fn = getattr(lib(), name)
-    if getattr(fn, "_s2st_bound", False):
-        return fn
-    ret, alist = header_prototypes()[name]
-    fn.restype = ret
-    fn.argtypes = [t for t, _ in alist]
-    fn._s2st_bound = True
-    return fn
+    return getattr(lib(), name)
 
 
 def call(name: str, *args):

@@ -34,10 +34,6 @@ class NativeComm:
         import ctypes as C
         from . import binding as bd
         self.C, self.bd, self.lib = C, bd, bd.lib()
-        self.lib.s2st_comm_unique_id.argtypes = [C.c_void_p]
-        self.lib.s2st_comm_init.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
-        self.lib.s2st_allreduce_sum_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        self.lib.s2st_comm_destroy.argtypes = [C.c_void_p]
         if not self.lib.s2st_comm_available():
             raise bd.S2STHipError("no RCCL library could be bound (s2st_comm_available() == 0)")
         world = dist.get_world_size() if dist.is_initialized() else 1

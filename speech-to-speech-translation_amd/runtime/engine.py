@@ -176,24 +176,6 @@ class Engine:
         self.device = device
         self.lib = bd.lib()
         self.cfg = config_from_args(args, precise)
-        self.lib.s2st_engine_create.argtypes = [C.POINTER(ModelConfig), C.POINTER(C.c_void_p)]
-        self.lib.s2st_engine_destroy.argtypes = [C.c_void_p]
-        self.lib.s2st_engine_destroy.restype = None
-        self.lib.s2st_engine_num_params.argtypes = [C.c_void_p]
-        self.lib.s2st_engine_param_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ParamInfo)]
-        self.lib.s2st_engine_param_floats.argtypes = [C.c_void_p]
-        self.lib.s2st_engine_param_floats.restype = C.c_int64
-        self.lib.s2st_engine_buffer_floats.argtypes = [C.c_void_p]
-        self.lib.s2st_engine_buffer_floats.restype = C.c_int64
-        self.lib.s2st_engine_bind.argtypes = [C.c_void_p] * 4
-        self.lib.s2st_engine_workspace_floats.argtypes = [C.c_void_p, C.POINTER(Batch)]
-        self.lib.s2st_engine_workspace_floats.restype = C.c_int64
-        self.lib.s2st_engine_forward.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs),
-                                                 C.c_void_p, C.c_int64, C.c_void_p]
-        self.lib.s2st_engine_backward.argtypes = [C.c_void_p, C.c_float, C.c_int32, C.c_void_p]
-        self.lib.s2st_engine_num_segments.argtypes = [C.c_void_p]
-        self.lib.s2st_engine_segment_range.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64),
-                                                       C.POINTER(C.c_int64)]
         h = C.c_void_p()
         bd.check(self.lib.s2st_engine_create(C.byref(self.cfg), C.byref(h)), "s2st_engine_create")
         self.h = h
@@ -217,12 +199,10 @@ class Engine:
         self.params_bf16 = None
         if not precise:
             self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device)
-            self.lib.s2st_engine_bind_bf16.argtypes = [C.c_void_p, C.c_void_p]
             self.lib.s2st_engine_bind_bf16(h, self.params_bf16.data_ptr())
             import os as _os
             if _os.environ.get("S2ST_NO_WT", "0") != "1":
                 self.params_bf16_t = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device)
-                self.lib.s2st_engine_bind_bf16_transposed.argtypes = [C.c_void_p, C.c_void_p]
                 self.lib.s2st_engine_bind_bf16_transposed(h, self.params_bf16_t.data_ptr())
         self.workspace: Optional[torch.Tensor] = None
         self._outpool: Optional[torch.Tensor] = None
@@ -255,9 +235,7 @@ class Engine:
             # (said to the engine itself -- s2st_engine_allow_side_stream -- not through the process environment: setenv
             #  races with the getenv calls other threads' launches make inside the library)
             tw = Engine(self.args, self.device, precise=bool(self.cfg.precise), share_with=self)
-            f = tw.lib.s2st_engine_allow_side_stream
-            f.argtypes = [C.c_void_p, C.c_int32]
-            bd.check(f(tw.h, 0), "s2st_engine_allow_side_stream")
+            bd.check(tw.lib.s2st_engine_allow_side_stream(tw.h, 0), "s2st_engine_allow_side_stream")
             tws.append(tw)
         return tws[:n]
 
@@ -621,12 +599,8 @@ class Engine:
         if c.has_st:
             o["tap1"] = torch.empty(B, E, c.enc_dim, device=dev)
             out.tap1 = o["tap1"].data_ptr()
-        self.lib.s2st_engine_decode_state_floats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        self.lib.s2st_engine_decode_state_floats.restype = C.c_int64
         n_state = int(self.lib.s2st_engine_decode_state_floats(self.h, B, E, max_steps))
         state = torch.zeros(n_state, dtype=torch.float32, device=dev)
-        self.lib.s2st_engine_decode_begin.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.c_void_p,
-                                                      C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         bd.check(self.lib.s2st_engine_decode_begin(self.h, C.byref(b), C.byref(out), state.data_ptr(), n_state,
                                                    max_steps, self.workspace.data_ptr(), self.workspace.numel(),
                                                    bd.stream_ptr()), "s2st_engine_decode_begin")
@@ -636,10 +610,8 @@ class Engine:
 
     def decode_row_map(self, row_map: Optional[torch.Tensor]):
         """After ``decode_begin`` of a MERGED batch: ``row_map`` [B] int32 (device) = every row's index inside its own batch."""
-        f = self.lib.s2st_engine_decode_row_map
-        f.argtypes = [C.c_void_p, C.c_void_p]
         self._dec["row_map"] = row_map  # (kept alive for the run)
-        bd.check(f(self.h, bd.ptr(row_map)), "s2st_engine_decode_row_map")
+        bd.check(self.lib.s2st_engine_decode_row_map(self.h, bd.ptr(row_map)), "s2st_engine_decode_row_map")
 
     def decode_buffers(self, max_steps: int):
         """Whole-run buffers of an AR decode (round 4: nothing is allocated, filled or uploaded per step): outputs
@@ -665,12 +637,10 @@ class Engine:
         d, c = self._dec, self.cfg
         b = d["bufs"]
         prev = b["bos"] if step == 0 else b["feat"][step - 1]
-        f = self.lib.s2st_engine_decode_step
-        f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        bd.check(f(self.h, step, prev.data_ptr(), b["pos"][step].data_ptr(), b["klen"].data_ptr(), seed,
-                   b["feat"][step].data_ptr(), b["eos"][step].data_ptr(), b["attn"][step].data_ptr(),
-                   self.workspace.data_ptr(), self.workspace.numel(), bd.stream_ptr()), "s2st_engine_decode_step")
+        bd.check(self.lib.s2st_engine_decode_step(
+            self.h, step, prev.data_ptr(), b["pos"][step].data_ptr(), b["klen"].data_ptr(), seed, b["feat"][step].data_ptr(),
+            b["eos"][step].data_ptr(), b["attn"][step].data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+            bd.stream_ptr()), "s2st_engine_decode_step")
         bd.call("s2st_decode_stop_update_i32", b["eos"][step], float(thr), step, int(max_iter), d["B"], b["finished"],
                 b["out_lens"], b["klen"], b["n_done"])
 
@@ -683,8 +653,6 @@ class Engine:
         False where the run's steps do not qualify (the caller keeps ``decode_step_into``)."""
         d, dev, c = self._dec, self.device, self.cfg
         lib = self.lib
-        lib.s2st_engine_decode_replay_supported.argtypes = [C.c_void_p]
-        lib.s2st_engine_decode_replay_supported.restype = C.c_int32
         if not int(lib.s2st_engine_decode_replay_supported(self.h)):
             return False
         B, E = d["B"], d["E"]
@@ -694,12 +662,6 @@ class Engine:
         st = DecodeReplay(*(r[k].data_ptr() for k in ("step", "seeds", "cur_feat", "cur_eos", "cur_attn", "pe_cur")))
         seed0 &= (1 << 64) - 1
         d["replay"] = dict(bufs=r, st=st, seed0=seed0, thr=float(thr), max_iter=int(max_iter), graph=None)
-        lib.s2st_engine_decode_replay_begin.argtypes = [C.c_void_p, C.POINTER(DecodeReplay), C.c_uint64, C.c_void_p]
-        lib.s2st_engine_decode_step_replay.argtypes = [C.c_void_p, C.POINTER(DecodeReplay), C.c_void_p, C.c_void_p, C.c_int64,
-                                                       C.c_void_p]
-        lib.s2st_engine_decode_replay_commit.argtypes = [C.c_void_p, C.POINTER(DecodeReplay), C.c_uint64, C.c_float, C.c_int32,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p]
         if graph and dev.type == "cuda":
             from . import streams
             g = torch.cuda.CUDAGraph()
@@ -745,9 +707,6 @@ class Engine:
         eos = torch.empty(B, device=dev)
         attn = torch.empty(B, E, device=dev) if want_attn else None
         klen = self_klen.to(dev, torch.int32).contiguous() if self_klen is not None else None
-        self.lib.s2st_engine_decode_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_int64, C.c_void_p]
         bd.check(self.lib.s2st_engine_decode_step(self.h, step, prev.data_ptr(), pos.data_ptr(), bd.ptr(klen), seed,
                                                   feat.data_ptr(),
                                                   eos.data_ptr(), bd.ptr(attn), self.workspace.data_ptr(),
@@ -763,8 +722,6 @@ class Engine:
         out = torch.empty_like(feat)
         need = 64 * B * (D + 8) * max(self.cfg.postnet_dim, self.cfg.out_dim) + (8 << 20)
         self._grow_workspace(need, need)
-        self.lib.s2st_engine_postnet_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                                      C.c_void_p, C.c_int64, C.c_void_p]
         bd.check(self.lib.s2st_engine_postnet_eval(self.h, feat.data_ptr(), B, D, out.data_ptr(),
                                                    self.workspace.data_ptr(), self.workspace.numel(), bd.stream_ptr()),
                  "s2st_engine_postnet_eval")
@@ -814,15 +771,11 @@ class Engine:
     # ---- dropout-site log (test instrumentation: include/s2st_hip.h, s2st_engine_site_log) ----------------------------
     def site_log(self, on: bool = True):
         """Make every later forward record its dropout sites (seed, kind, p, element geometry, place)."""
-        f = self.lib.s2st_engine_site_log
-        f.argtypes = [C.c_void_p, C.c_int32]
-        bd.check(f(self.h, 1 if on else 0), "s2st_engine_site_log")
+        bd.check(self.lib.s2st_engine_site_log(self.h, 1 if on else 0), "s2st_engine_site_log")
 
     def dropout_sites(self) -> Dict[str, "DropoutSite"]:
         """The last forward's sites by name ``<ctx>/<kind><ordinal>`` (e.g. ``enc.L3/lin1``, ``dec.L0/attn1``, ``post/norm2``)."""
         f = self.lib.s2st_engine_site_log_get
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        f.restype = C.c_int32
         n = int(f(self.h, None, 0))
         recs = (DropoutSite * max(n, 1))()
         f(self.h, C.cast(recs, C.c_void_p), n)
@@ -852,8 +805,6 @@ class Engine:
         """torch view of the engine's second stream (None on the emulator / when disabled)."""
         if bd.is_emulator() or not torch.cuda.is_available():
             return None
-        self.lib.s2st_engine_side_stream.argtypes = [C.c_void_p]
-        self.lib.s2st_engine_side_stream.restype = C.c_void_p
         p = self.lib.s2st_engine_side_stream(self.h)
         return torch.cuda.ExternalStream(p) if p else None
 
@@ -884,9 +835,6 @@ class Engine:
         """``s2st_engine_adam_overlapped``: the fused scale / clip / Adam update in chunks on the engine's second stream;
         the next ``forward`` waits chunk by chunk.  Anything else that reads the parameters calls ``wait_optimizer``."""
         f = self.lib.s2st_engine_adam_overlapped
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_float, C.c_float,
-                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                      C.c_void_p]
         for t in (exp_avg, exp_avg_sq, sumsq_parts, gnorm_out, skipped):
             bd.require_device(t)
         bd.check(f(self.h, exp_avg.data_ptr(), exp_avg_sq.data_ptr(), sumsq_parts.data_ptr(), int(n_parts), float(gmul),
@@ -896,9 +844,7 @@ class Engine:
 
     def wait_optimizer(self):
         """The current stream waits for an overlapped update still in flight (no-op otherwise)."""
-        f = self.lib.s2st_engine_wait_optimizer
-        f.argtypes = [C.c_void_p, C.c_void_p]
-        bd.check(f(self.h, bd.stream_ptr()), "s2st_engine_wait_optimizer")
+        bd.check(self.lib.s2st_engine_wait_optimizer(self.h, bd.stream_ptr()), "s2st_engine_wait_optimizer")
 
     def zero_grad(self):
         self.grads.zero_()

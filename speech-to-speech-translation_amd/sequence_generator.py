@@ -45,11 +45,6 @@ class AuxSequenceGenerator:
         eng = model.engine
         if not (eng.cfg.has_asr if which == "asr" else eng.cfg.has_st):
             raise ValueError(f"the model has no aux {which} decoder")
-        lib = eng.lib
-        lib.s2st_engine_aux_decode_workspace.argtypes = [C.c_void_p] + [C.c_int32] * 4
-        lib.s2st_engine_aux_decode_workspace.restype = C.c_int64
-        lib.s2st_engine_aux_decode.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + \
-            [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 
     # -- decoder forward on the device: tokens [Bb, L] (host int64) -> lprobs of the last position [Bb, V] (host fp32)
     def _step_lprobs(self, tap, enc_lens_dev, tokens: np.ndarray, E: int) -> np.ndarray:
@@ -60,8 +55,7 @@ class AuxSequenceGenerator:
         need = int(eng.lib.s2st_engine_aux_decode_workspace(eng.h, w, Bb, L, E))
         if need < 0:
             raise bd.S2STHipError(f"s2st_engine_aux_decode_workspace failed ({need})")
-        if eng.workspace is None or eng.workspace.numel() < need:
-            eng.workspace = torch.empty(int(need * 1.25) + 4096, dtype=torch.float32, device=dev)
+        eng._grow_workspace(need, int(need * 1.25) + 4096)
         tok = torch.from_numpy(np.ascontiguousarray(tokens)).to(dev)
         m = (tokens != PAD).astype(np.int64)
         pos = torch.from_numpy((np.cumsum(m, axis=1) * m + PAD).astype(np.int32)).to(dev)  # make_positions (utils.py:254-264)
@@ -84,19 +78,11 @@ class AuxSequenceGenerator:
         lib = eng.lib
         w = 0 if self.which == "asr" else 1
         Bb = tap.shape[0]
-        lib.s2st_engine_aux_inc_state_floats.argtypes = [C.c_void_p] + [C.c_int32] * 4
-        lib.s2st_engine_aux_inc_state_floats.restype = C.c_int64
-        lib.s2st_engine_aux_inc_workspace.argtypes = [C.c_void_p] + [C.c_int32] * 3
-        lib.s2st_engine_aux_inc_workspace.restype = C.c_int64
-        lib.s2st_engine_aux_inc_begin.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + \
-            [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.s2st_engine_aux_inc_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
         n = int(lib.s2st_engine_aux_inc_state_floats(eng.h, w, Bb, E, max_len + 2))
         need = int(lib.s2st_engine_aux_inc_workspace(eng.h, w, Bb, E))
         if n < 0 or need < 0:
             raise bd.S2STHipError(f"s2st_engine_aux_inc_state_floats / _workspace failed ({n}, {need})")
-        if eng.workspace is None or eng.workspace.numel() < need:
-            eng.workspace = torch.empty(int(need * 1.25) + 4096, dtype=torch.float32, device=dev)
+        eng._grow_workspace(need, int(need * 1.25) + 4096)
         state = torch.zeros(n, dtype=torch.float32, device=dev)
         bd.check(lib.s2st_engine_aux_inc_begin(eng.h, w, tap.data_ptr(), enc_lens_dev.data_ptr(), Bb, E, max_len + 2,
                                                state.data_ptr(), eng.workspace.data_ptr(), eng.workspace.numel(), bd.stream_ptr()),

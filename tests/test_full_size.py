@@ -370,7 +370,9 @@ def test_overlapped_optimizer_update_gives_the_same_trajectory(backend, workload
     forward waits chunk by chunk (s2st_engine_adam_overlapped).  Every sum of a step is ordered, so the trajectory is a
     bit-exact function of (parameters, batches, seeds): five updates at base size with the recipe's dropouts end on the
     SAME bits with and without the overlap -- a forward that read a parameter chunk before its update landed would not.
-    (On the emulator there is no second stream: the chunked update itself is what is compared.)"""
+    An evaluation entry point called right after the last update, without ``wait_optimizer()``, waits for it itself: its
+    post-net output is the same bits too.  (On the emulator there is no second stream: the chunked update itself is what
+    is compared.)"""
     PKG = ENG.rsplit(".runtime", 1)[0]
     tasks = importlib.import_module(PKG + ".tasks")
     tr = importlib.import_module(PKG + ".trainer")
@@ -392,15 +394,19 @@ def test_overlapped_optimizer_update_gives_the_same_trajectory(backend, workload
         model = task.build_model(a)
         load_synth(model, 0)
         t = tr.Trainer(a, task, model, task.build_criterion(a))
+        feat = torch.randn(2, 7, model.engine.cfg.out_dim, generator=torch.Generator().manual_seed(5)).to(backend.device)
+        model.engine.postnet_eval(feat)  # (sizes the workspace now: growing it later would synchronise the device)
         gn = []
         for u in range(5):
             r = t.train_step([batches[u % len(batches)]], overlap_optimizer=overlap)
             gn.append(r["gnorm"])  # (read after the loop: no host sync between the updates)
+        post = model.engine.postnet_eval(feat)  # straight after the last update: no wait_optimizer() first
         t.wait_optimizer()
         backend.sync()
-        runs.append((model.engine.params.clone(), t.exp_avg.clone(), float(gn[-1][0]), int(t.skipped)))
+        runs.append((model.engine.params.clone(), t.exp_avg.clone(), float(gn[-1][0]), int(t.skipped), post))
         del t, model, task
-    (p0, m0, g0, s0), (p1, m1, g1, s1), (p2, m2, g2, s2) = runs
+    (p0, m0, g0, s0, q0), (p1, m1, g1, s1, q1), (p2, m2, g2, s2, q2) = runs
     assert s0 == s1 == s2 == 0 and np.isfinite(g0)
+    assert torch.isfinite(q0).all() and torch.equal(q0, q1) and torch.equal(q1, q2)
     assert torch.equal(p1, p2) and torch.equal(m1, m2)  # the overlapped schedule repeats itself ...
     assert torch.equal(p0, p1) and torch.equal(m0, m1) and g0 == g1  # ... and equals the plain one

@@ -118,6 +118,25 @@ def test_batch_is_bit_identical_to_one_at_a_time(backend, precise):
         assert bool((wave[u, n:] == 0.0).all())
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("backend", ["hip"], indirect=True)
+def test_forward_on_a_second_stream_after_a_refresh(backend):
+    """After a parameter write the next forward casts the bf16 copy on its own stream; a forward on another stream right
+    after it (no ordering between the two streams) must wait for that cast, and computes the same wave."""
+    voc = _vocoder(backend, "v1", False)
+    mel = HS.synth_mel(32, 7)
+    voc(mel)
+    backend.sync()
+    voc.params.mul_(0.5)  # (bumps the version: the next forward refreshes the copy)
+    a = voc(mel)
+    s = torch.cuda.Stream(device=backend.device)
+    with torch.cuda.stream(s):
+        b = voc(mel)
+    backend.sync()
+    assert torch.isfinite(a).all() and torch.equal(a, b)
+    assert torch.equal(voc(mel), a)
+
+
 def test_weight_norm_fold_per_input_channel_for_transposed_convs():
     """ConvTranspose1d's weight is [C_in, C_out, k]: weight_norm(dim=0) normalises per INPUT channel; the fold agrees
     with torch's own weight_norm module, and differs from a per-output-channel norm on this case."""

@@ -31,6 +31,35 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.s2st_version() >= 100
 
 
+@pytest.mark.parametrize("backend", ["emu"], indirect=True)
+def test_every_called_entry_point_is_declared_and_bound(backend):
+    """The package reaches the library only through names include/s2st_hip.h declares (``lib.<name>``,
+    ``bd.call("<name>")``), and load_library gives every exported declared function its header signature."""
+    import re
+    bd = backend.bd
+    protos = bd.header_prototypes()
+    called = set()
+    for dirpath, _, files in os.walk(os.path.join(ROOT, PKG)):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(dirpath, f)).read()
+                called |= set(re.findall(r"\blib(?:\(\))?\.(s2st_\w+)", src))
+                called |= set(re.findall(r"\b(?:call|_bind)\(\s*\"(s2st_\w+)\"", src))
+    assert len(called) >= 60 and "s2st_engine_side_stream" in called
+    assert not called - set(protos), sorted(called - set(protos))
+    prev = (bd._lib, bd._lib_is_emulator)
+    try:
+        lib = bd.load_library(os.path.join(ROOT, "tests", "hipemu", "_build", "libs2st_emu.so"), emulator=True)
+        exported = [n for n in protos if hasattr(lib, n)]
+        assert len(exported) >= 100
+        for name in exported:
+            ret, args = protos[name]
+            fn = getattr(lib, name)
+            assert fn.argtypes == [t for t, _ in args] and fn.restype is ret, name
+    finally:
+        bd._lib, bd._lib_is_emulator = prev
+
+
 def test_no_cpu_fallback():
     """Product binding refuses CPU tensors (only the test-suite may load the emulator build)."""
     bd = importlib.import_module(PKG + ".runtime.binding")
