@@ -12,6 +12,11 @@ pre/post-net .5) plus CTC; batches packed by the reference's batch_by_size rule 
 max-tokens=20000.  One "step" = one optimizer update on one batch per rank (update-freq 1);
 rank r takes batches r, r+W, ... (weak scaling: per-GPU work fixed).  Inputs are resident in
 HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints that line.  The legs that measure
+anything else -- the host-fed steps, the per-dispatch roofline replay, the CPU baseline, the other single-GPU
+configurations, and for --config infer_base the device-generator, early-stop and serial passes and the MCD against the
+CPU path -- run only with --full, after the timed steps and the dump.
 """
 import argparse
 import importlib
@@ -307,155 +312,158 @@ def infer_main(args):
         arrays = {k: torch.cat([h[k].reshape(-1) for h in last_hypos]) for k in keys}
         arrays["lengths"] = torch.tensor([float(h["feature"].shape[0]) for h in last_hypos], dtype=torch.float64)
         dump_outputs(args.dump_outputs, arrays)
-    # the same pass with the initial phases drawn by the device's generator instead of numpy's (GriffinLim(phase_rng="device"):
-    # same distribution, no host-side generator run) -- reported next to `value`, never as it
-    voc_d = V.GriffinLimVocoder(spec_bwd_max_iter=INFER_GL_ITERS, device=dev, phase_rng="device", **voc_kw)
-    gens_d = [G.AutoRegressiveSpeechGenerator(model, voc_d, None, max_iter=it, eos_prob_threshold=2.0) for it in iters]
-    run(gens_d, max(4, len(samples)))  # (its vocoder's buffers and second stream exist before the clock starts)
-    torch.cuda.synchronize()
-    t0d = time.perf_counter()
-    nd, _ = run(gens_d, args.steps)
-    torch.cuda.synchronize()
-    value_device_rng = nd / (time.perf_counter() - t0d)
-    # ---- the same pass with EARLY STOPS: the headline's stop threshold is never reached (fixed work, SURVEY
-    #      8(d)), which also means no utterance ever leaves the batch early and every run-ahead phase draw is used -- not what
-    #      a trained checkpoint does.  Random-init weights give every (utterance, step) some stop probability: the threshold
-    #      is set to the median over the utterances of their largest probability in the first 70 % of the steps, so about
-    #      half of them stop somewhere in there and the rest later or never; the batch ends when its last utterance has.
-    with torch.no_grad():
-        probe = G.AutoRegressiveSpeechGenerator(model, None, None, max_iter=iters[0], eos_prob_threshold=2.0).generate(model, samples[0])
-    nf = a.n_frames_per_step
-    peak = torch.stack([f["eos_prob"][::nf][: max(1, int(0.7 * iters[0]))].max() for f in probe])
-    thr_e = float(peak.median())
-    gens_e = [G.AutoRegressiveSpeechGenerator(model, voc, None, max_iter=it, eos_prob_threshold=thr_e) for it in iters]
-    run(gens_e, max(2, len(samples)))
-    torch.cuda.synchronize()
-    t0e = time.perf_counter()
-    ne, nfe = run(gens_e, args.steps)
-    torch.cuda.synchronize()
-    dte = time.perf_counter() - t0e
-    early = {"threshold": round(thr_e, 5), "utterances_per_s": round(ne / dte, 2), "mel_frames_per_s": round(nfe / dte, 1),
-             "mean_decoded_fraction_of_the_fixed_work": round(nfe / max(n_frames, 1), 3),
-             "note": "same batches, weights, chains and vocoder overlap as `value`, stop threshold = median over utterances of "
-                     "their peak stop probability in the first 70 % of the steps (random-init weights): utterances leave at "
-                     "different steps, Griffin-Lim runs on what was decoded"}
-    vlog("early-stop leg", early)
-    # ... and strictly one after the other (the vocoder on the decoder's stream), for the record
-    t0s = time.perf_counter()
-    for i in range(args.steps):
-        gens[i % len(samples)].generate(model, samples[i % len(samples)])
-    torch.cuda.synchronize()
-    value_serial = args.steps * len(samples[0]["id"]) / (time.perf_counter() - t0s) if len(samples) == 1 else None
-    # decode / vocoder split of one batch (un-timed above)
-    tA = time.perf_counter()
-    g0 = G.AutoRegressiveSpeechGenerator(model, None, None, max_iter=iters[0], eos_prob_threshold=2.0)
-    f0 = g0.generate(model, samples[0])
-    torch.cuda.synchronize()
-    t_dec = time.perf_counter() - tA
-    tA = time.perf_counter()
-    voc.batch([f["feature"] for f in f0])
-    torch.cuda.synchronize()
-    t_voc = time.perf_counter() - tA
-
-    # ---- roofline: replay one pass over the batches with per-dispatch timing; the kernel with the largest share --------
-    roofline = None
-    if not args.no_roofline:
-        import ctypes as C
-        lib = bd.lib()
-        lib.s2st_profile_enable.argtypes = [C.c_int32]
-        lib.s2st_profile_report.argtypes = [C.c_char_p, C.c_int64]
-        lib.s2st_profile_report.restype = C.c_int64
-        lib.s2st_profile_enable(1)
-        for i in range(len(samples)):  # (one stream: the per-dispatch events belong to one queue)
-            gens[i].generate(model, samples[i])
+    # ---- --full only: the legs beside the headline ------------------------------------------------------------------
+    value_device_rng = early = value_serial = t_dec = t_voc = roofline = cpu = mcd = None
+    if args.full:
+        # the same pass with the initial phases drawn by the device's generator instead of numpy's (GriffinLim(phase_rng="device"):
+        # same distribution, no host-side generator run) -- reported next to `value`, never as it
+        voc_d = V.GriffinLimVocoder(spec_bwd_max_iter=INFER_GL_ITERS, device=dev, phase_rng="device", **voc_kw)
+        gens_d = [G.AutoRegressiveSpeechGenerator(model, voc_d, None, max_iter=it, eos_prob_threshold=2.0) for it in iters]
+        run(gens_d, max(4, len(samples)))  # (its vocoder's buffers and second stream exist before the clock starts)
         torch.cuda.synchronize()
-        lib.s2st_profile_enable(0)
-        buf = C.create_string_buffer(1 << 16)
-        n = lib.s2st_profile_report(buf, len(buf))
-        rows = {}
-        for ln in buf.value.decode().splitlines() if n > 0 else []:
-            tag, cnt, us, w1, w2 = ln.split("\t")
-            rows[tag] = dict(n=int(cnt), us=float(us), work=float(w1), work2=float(w2))
-        if os.environ.get("S2ST_BENCH_VERBOSE"):
-            for tag, r in sorted(rows.items(), key=lambda kv: -kv[1]["us"])[:25]:
-                vlog("  %-60s launches %7d  avg %7.2f us  total ms %8.3f" % (tag, r["n"], r["us"] / r["n"], r["us"] * 1e-3))
-        if rows:
-            tot_us = sum(r["us"] for r in rows.values())
-            dom_tag, dom = max(rows.items(), key=lambda kv: kv[1]["us"])
-            avg_us = dom["us"] / dom["n"]
-            # (the skinny-M decode GEMM streams its weights once per launch: HBM / L2-bound, its work figure is bytes)
-            is_mfma = dom_tag.startswith(("gemm", "flash_")) and dom["work"] > 0 and dom_tag != "gemm_skinny_kernel"
-            if is_mfma:
-                ach = dom["work"] / dom["n"] / (avg_us * 1e-6) / 1e12
-                roofline = {"bound": "mfma", "kernel": dom_tag, "achieved": round(ach, 2), "peak": MFMA_BF16_PEAK_TFLOPS,
-                            "unit": "TFLOP/s", "frac": round(ach / MFMA_BF16_PEAK_TFLOPS, 5), "traffic": None,
-                            "gflop_per_launch": round(dom["work"] / dom["n"] / 1e9, 3)}
-            else:
-                ach = dom["work"] / dom["n"] / (avg_us * 1e-6) / 1e9 if dom["work"] > 0 else None
-                roofline = {"bound": "hbm", "kernel": dom_tag, "achieved": None if ach is None else round(ach, 1),
-                            "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None if ach is None else round(ach / HBM_PEAK_GBPS, 5),
-                            "traffic": None}
-            roofline.update({"avg_launch_us": round(avg_us, 2), "launches_per_utterance": round(dom["n"] / INFER_N_UTTS, 1),
-                             "share_of_kernel_time": round(dom["us"] / tot_us, 4),
-                             "kernel_ms_per_utterance": round(tot_us * 1e-3 / INFER_N_UTTS, 3),
-                             "launches_per_utterance_all_kernels": round(sum(r["n"] for r in rows.values()) / INFER_N_UTTS, 1),
-                             "timing": "start/stop events attached to each dispatch, one pass over the %d batches" % len(samples)})
-
-    # ---- CPU leg + MCD of the GPU path against the CPU path on the same inputs (Prenet dropout 0 on both sides: the
-    #      reference's always-on Prenet dropout makes the decode a random variable; the timed workload above keeps it on) --
-    cpu, mcd = None, None
-    if args.cpu_seconds > 0:
-        import subprocess
-        import tempfile
-        n_cpu = args.cpu_utts or 8
-        # utterances around the corpus' median length (the CPU oracle re-runs its decoder on the whole prefix every step:
-        # ~1 s per utterance here; `--cpu-utts 64` = all of them, the run committed under profiles/)
-        mid = len(order) // 2
-        ids = order[max(0, mid - n_cpu // 2): max(0, mid - n_cpu // 2) + n_cpu].tolist() if n_cpu < len(order) else order.tolist()
-        sub = corpus.collate_batch(ids)
-        sub["net_input"]["collated_audios_orig"] = None
-        sub["net_input"]["padding_mask"] = None
-        mi = int(sub["target_lengths"].max())
-        a0 = C_.recipe_args("base_recipe", prenet_dropout=0.0)
-        m0 = tasks.S2ST_TranslationTask.setup_task(a0, device=dev).build_model(a0)
-        m0.load_state_dict(model.state_dict(), strict=True)
-        rs = np.random.RandomState(5)
-        F_ = voc_kw["n_fft"] // 2 + 1
-        # (the reference's initial phases, vocoder.py:101-102, here from a seeded generator and shared with the CPU leg)
-        angles = [np.angle(np.exp(2j * np.pi * rs.rand(F_, mi * a0.n_frames_per_step))).astype(np.float32) for _ in ids]
-        g_ = G.AutoRegressiveSpeechGenerator(m0, None, None, max_iter=mi, eos_prob_threshold=2.0)
-        fin0 = g_.generate(m0, sub)
-        waves_gpu = voc.batch([f["feature"] for f in fin0], angles)
+        t0d = time.perf_counter()
+        nd, _ = run(gens_d, args.steps)
         torch.cuda.synchronize()
-        with tempfile.TemporaryDirectory() as td:
-            job = {"state": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "ids": ids, "max_iter": mi,
-                   "angles": angles, "voc": voc_kw, "out": os.path.join(td, "cpu_out.npz")}
-            jp = os.path.join(td, "job.pt")
-            torch.save(job, jp)
-            try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-leg", "infer:" + jp],
-                                   capture_output=True, text=True, timeout=10 * args.cpu_seconds + 300)
-                for ln in r.stdout.splitlines():
-                    if ln.startswith("{"):
-                        cpu = json.loads(ln)
-                if cpu is None:
-                    vlog("cpu leg produced no result:", r.stderr[-600:])
+        value_device_rng = nd / (time.perf_counter() - t0d)
+        # ---- the same pass with EARLY STOPS: the headline's stop threshold is never reached (fixed work, SURVEY
+        #      8(d)), which also means no utterance ever leaves the batch early and every run-ahead phase draw is used -- not what
+        #      a trained checkpoint does.  Random-init weights give every (utterance, step) some stop probability: the threshold
+        #      is set to the median over the utterances of their largest probability in the first 70 % of the steps, so about
+        #      half of them stop somewhere in there and the rest later or never; the batch ends when its last utterance has.
+        with torch.no_grad():
+            probe = G.AutoRegressiveSpeechGenerator(model, None, None, max_iter=iters[0], eos_prob_threshold=2.0).generate(model, samples[0])
+        nf = a.n_frames_per_step
+        peak = torch.stack([f["eos_prob"][::nf][: max(1, int(0.7 * iters[0]))].max() for f in probe])
+        thr_e = float(peak.median())
+        gens_e = [G.AutoRegressiveSpeechGenerator(model, voc, None, max_iter=it, eos_prob_threshold=thr_e) for it in iters]
+        run(gens_e, max(2, len(samples)))
+        torch.cuda.synchronize()
+        t0e = time.perf_counter()
+        ne, nfe = run(gens_e, args.steps)
+        torch.cuda.synchronize()
+        dte = time.perf_counter() - t0e
+        early = {"threshold": round(thr_e, 5), "utterances_per_s": round(ne / dte, 2), "mel_frames_per_s": round(nfe / dte, 1),
+                 "mean_decoded_fraction_of_the_fixed_work": round(nfe / max(n_frames, 1), 3),
+                 "note": "same batches, weights, chains and vocoder overlap as `value`, stop threshold = median over utterances of "
+                         "their peak stop probability in the first 70 % of the steps (random-init weights): utterances leave at "
+                         "different steps, Griffin-Lim runs on what was decoded"}
+        vlog("early-stop leg", early)
+        # ... and strictly one after the other (the vocoder on the decoder's stream), for the record
+        t0s = time.perf_counter()
+        for i in range(args.steps):
+            gens[i % len(samples)].generate(model, samples[i % len(samples)])
+        torch.cuda.synchronize()
+        value_serial = args.steps * len(samples[0]["id"]) / (time.perf_counter() - t0s) if len(samples) == 1 else None
+        # decode / vocoder split of one batch (un-timed above)
+        tA = time.perf_counter()
+        g0 = G.AutoRegressiveSpeechGenerator(model, None, None, max_iter=iters[0], eos_prob_threshold=2.0)
+        f0 = g0.generate(model, samples[0])
+        torch.cuda.synchronize()
+        t_dec = time.perf_counter() - tA
+        tA = time.perf_counter()
+        voc.batch([f["feature"] for f in f0])
+        torch.cuda.synchronize()
+        t_voc = time.perf_counter() - tA
+
+        # ---- roofline: replay one pass over the batches with per-dispatch timing; the kernel with the largest share --------
+        roofline = None
+        if not args.no_roofline:
+            import ctypes as C
+            lib = bd.lib()
+            lib.s2st_profile_enable.argtypes = [C.c_int32]
+            lib.s2st_profile_report.argtypes = [C.c_char_p, C.c_int64]
+            lib.s2st_profile_report.restype = C.c_int64
+            lib.s2st_profile_enable(1)
+            for i in range(len(samples)):  # (one stream: the per-dispatch events belong to one queue)
+                gens[i].generate(model, samples[i])
+            torch.cuda.synchronize()
+            lib.s2st_profile_enable(0)
+            buf = C.create_string_buffer(1 << 16)
+            n = lib.s2st_profile_report(buf, len(buf))
+            rows = {}
+            for ln in buf.value.decode().splitlines() if n > 0 else []:
+                tag, cnt, us, w1, w2 = ln.split("\t")
+                rows[tag] = dict(n=int(cnt), us=float(us), work=float(w1), work2=float(w2))
+            if os.environ.get("S2ST_BENCH_VERBOSE"):
+                for tag, r in sorted(rows.items(), key=lambda kv: -kv[1]["us"])[:25]:
+                    vlog("  %-60s launches %7d  avg %7.2f us  total ms %8.3f" % (tag, r["n"], r["us"] / r["n"], r["us"] * 1e-3))
+            if rows:
+                tot_us = sum(r["us"] for r in rows.values())
+                dom_tag, dom = max(rows.items(), key=lambda kv: kv[1]["us"])
+                avg_us = dom["us"] / dom["n"]
+                # (the skinny-M decode GEMM streams its weights once per launch: HBM / L2-bound, its work figure is bytes)
+                is_mfma = dom_tag.startswith(("gemm", "flash_")) and dom["work"] > 0 and dom_tag != "gemm_skinny_kernel"
+                if is_mfma:
+                    ach = dom["work"] / dom["n"] / (avg_us * 1e-6) / 1e12
+                    roofline = {"bound": "mfma", "kernel": dom_tag, "achieved": round(ach, 2), "peak": MFMA_BF16_PEAK_TFLOPS,
+                                "unit": "TFLOP/s", "frac": round(ach / MFMA_BF16_PEAK_TFLOPS, 5), "traffic": None,
+                                "gflop_per_launch": round(dom["work"] / dom["n"] / 1e9, 3)}
                 else:
-                    z = np.load(job["out"])
-                    y_cpu = [torch.from_numpy(z[f"wave.{i}"]).to(dev) for i in range(len(ids))]
-                    y_gpu = [w.reshape(-1).float() for w in waves_gpu]
-                    res = M.batch_mel_cepstral_distortion(y_gpu, y_cpu, voc_kw["sample_rate"], "path", device=dev)
-                    ferr = max(float((f["feature"].cpu() - torch.from_numpy(z[f"feature.{i}"])).abs().max())
-                               for i, f in enumerate(fin0))
-                    mcd = {"mcd_gpu_vs_cpu": round(float(sum(float(d) for d, _ in res) / len(res)), 4),
-                           "utterances": len(ids), "max_abs_feature_diff": round(ferr, 5),
-                           "note": "MFCC distance along the DTW path between the GPU path's waveform (bf16 operands) and the "
-                                   "CPU oracle's (fp32) for the same weights, inputs, Prenet dropout 0 and initial phases; "
-                                   "0 = identical.  Both sides use this repository's restatements of two third-party tables "
-                                   "that are absent from the image (librosa's Slaney mel filters, torchaudio's MFCC): the "
-                                   "figure compares the two paths with each other, its absolute scale is unpinned"}
-            except subprocess.TimeoutExpired:
-                vlog("cpu leg timed out")
+                    ach = dom["work"] / dom["n"] / (avg_us * 1e-6) / 1e9 if dom["work"] > 0 else None
+                    roofline = {"bound": "hbm", "kernel": dom_tag, "achieved": None if ach is None else round(ach, 1),
+                                "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None if ach is None else round(ach / HBM_PEAK_GBPS, 5),
+                                "traffic": None}
+                roofline.update({"avg_launch_us": round(avg_us, 2), "launches_per_utterance": round(dom["n"] / INFER_N_UTTS, 1),
+                                 "share_of_kernel_time": round(dom["us"] / tot_us, 4),
+                                 "kernel_ms_per_utterance": round(tot_us * 1e-3 / INFER_N_UTTS, 3),
+                                 "launches_per_utterance_all_kernels": round(sum(r["n"] for r in rows.values()) / INFER_N_UTTS, 1),
+                                 "timing": "start/stop events attached to each dispatch, one pass over the %d batches" % len(samples)})
+
+        # ---- CPU leg + MCD of the GPU path against the CPU path on the same inputs (Prenet dropout 0 on both sides: the
+        #      reference's always-on Prenet dropout makes the decode a random variable; the timed workload above keeps it on) --
+        cpu, mcd = None, None
+        if args.cpu_seconds > 0:
+            import subprocess
+            import tempfile
+            n_cpu = args.cpu_utts or 8
+            # utterances around the corpus' median length (the CPU oracle re-runs its decoder on the whole prefix every step:
+            # ~1 s per utterance here; `--cpu-utts 64` = all of them, the run committed under profiles/)
+            mid = len(order) // 2
+            ids = order[max(0, mid - n_cpu // 2): max(0, mid - n_cpu // 2) + n_cpu].tolist() if n_cpu < len(order) else order.tolist()
+            sub = corpus.collate_batch(ids)
+            sub["net_input"]["collated_audios_orig"] = None
+            sub["net_input"]["padding_mask"] = None
+            mi = int(sub["target_lengths"].max())
+            a0 = C_.recipe_args("base_recipe", prenet_dropout=0.0)
+            m0 = tasks.S2ST_TranslationTask.setup_task(a0, device=dev).build_model(a0)
+            m0.load_state_dict(model.state_dict(), strict=True)
+            rs = np.random.RandomState(5)
+            F_ = voc_kw["n_fft"] // 2 + 1
+            # (the reference's initial phases, vocoder.py:101-102, here from a seeded generator and shared with the CPU leg)
+            angles = [np.angle(np.exp(2j * np.pi * rs.rand(F_, mi * a0.n_frames_per_step))).astype(np.float32) for _ in ids]
+            g_ = G.AutoRegressiveSpeechGenerator(m0, None, None, max_iter=mi, eos_prob_threshold=2.0)
+            fin0 = g_.generate(m0, sub)
+            waves_gpu = voc.batch([f["feature"] for f in fin0], angles)
+            torch.cuda.synchronize()
+            with tempfile.TemporaryDirectory() as td:
+                job = {"state": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "ids": ids, "max_iter": mi,
+                       "angles": angles, "voc": voc_kw, "out": os.path.join(td, "cpu_out.npz")}
+                jp = os.path.join(td, "job.pt")
+                torch.save(job, jp)
+                try:
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-leg", "infer:" + jp],
+                                       capture_output=True, text=True, timeout=10 * args.cpu_seconds + 300)
+                    for ln in r.stdout.splitlines():
+                        if ln.startswith("{"):
+                            cpu = json.loads(ln)
+                    if cpu is None:
+                        vlog("cpu leg produced no result:", r.stderr[-600:])
+                    else:
+                        z = np.load(job["out"])
+                        y_cpu = [torch.from_numpy(z[f"wave.{i}"]).to(dev) for i in range(len(ids))]
+                        y_gpu = [w.reshape(-1).float() for w in waves_gpu]
+                        res = M.batch_mel_cepstral_distortion(y_gpu, y_cpu, voc_kw["sample_rate"], "path", device=dev)
+                        ferr = max(float((f["feature"].cpu() - torch.from_numpy(z[f"feature.{i}"])).abs().max())
+                                   for i, f in enumerate(fin0))
+                        mcd = {"mcd_gpu_vs_cpu": round(float(sum(float(d) for d, _ in res) / len(res)), 4),
+                               "utterances": len(ids), "max_abs_feature_diff": round(ferr, 5),
+                               "note": "MFCC distance along the DTW path between the GPU path's waveform (bf16 operands) and the "
+                                       "CPU oracle's (fp32) for the same weights, inputs, Prenet dropout 0 and initial phases; "
+                                       "0 = identical.  Both sides use this repository's restatements of two third-party tables "
+                                       "that are absent from the image (librosa's Slaney mel filters, torchaudio's MFCC): the "
+                                       "figure compares the two paths with each other, its absolute scale is unpinned"}
+                except subprocess.TimeoutExpired:
+                    vlog("cpu leg timed out")
 
     value = n_utt / dt
     line = {"metric": "utterances/sec (AR mel decode + Griffin-Lim %d it) on Fisher-shaped inputs" % INFER_GL_ITERS,
@@ -470,18 +478,20 @@ def infer_main(args):
                                                                         "+".join(str(len(g)) for g in groups), INFER_GL_ITERS),
                        "name": "infer_base", "utterances_per_step": len(groups[0]), "mel_frames_per_s": round(n_frames / dt, 1),
                        "initial_phases": "numpy global generator on the host (the reference's draws, vocoder.py:101-102)",
-                       "value_with_device_phase_rng": round(value_device_rng, 2),
                        "vocoder_overlap": ("batch k's Griffin-Lim on a second stream beside batch k + 1's decoding steps"
                                            if DEFER else "off"),
-                       "decode_chains": CHAINS, "early_stop": early,
+                       "decode_chains": CHAINS,
                        # roles of the package's stream pool for which no free hardware queue was found (runtime/streams.py)
                        "stream_collisions": importlib.import_module(PKG + ".runtime.streams").collisions(),
                        "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "4 (runtime default)"),
-                       "value_without_vocoder_overlap": round(value_serial, 2) if value_serial else None,
-                       "decode_steps_per_batch": iters, "batch0_decode_ms": round(t_dec * 1e3, 2),
-                       "batch0_vocoder_alone_ms": round(t_voc * 1e3, 2),
-                       "batch0_note": "vocoder alone = called by itself, its phase draws NOT run ahead under the decode as they "
-                                      "are inside generate() (vocoder.GriffinLim.prefetch_phases)"}}
+                       "decode_steps_per_batch": iters}}
+    if args.full:
+        line["config"].update({
+            "value_with_device_phase_rng": round(value_device_rng, 2), "early_stop": early,
+            "value_without_vocoder_overlap": round(value_serial, 2) if value_serial else None,
+            "batch0_decode_ms": round(t_dec * 1e3, 2), "batch0_vocoder_alone_ms": round(t_voc * 1e3, 2),
+            "batch0_note": "vocoder alone = called by itself, its phase draws NOT run ahead under the decode as they are "
+                           "inside generate() (vocoder.GriffinLim.prefetch_phases)"})
     if roofline:
         line["roofline"] = roofline
     if cpu:
@@ -564,15 +574,20 @@ def main():
     ap.add_argument("--config", default="base_recipe")
     ap.add_argument("--max-tokens", type=int, default=20000)
     ap.add_argument("--n-utts", type=int, default=4096)
-    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="time budget of the CPU-baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run the legs that measure anything else: host-fed steps, "
+                         "the per-dispatch roofline replay, the CPU baseline, the other single-GPU configurations (infer_base: "
+                         "the device-generator, early-stop and serial passes and the MCD against the CPU path); the --no-* "
+                         "and --cpu-* options below select among them")
+    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="--full: time budget of the CPU-baseline leg (0 = skip)")
     ap.add_argument("--cpu-utts", type=int, default=0, help="CPU leg: first N utterances of timed batch 0 (0 = the "
                     "whole batch; default 8 for the HuBERT configuration, whose CPU front end is ~10x the model)")
     ap.add_argument("--cpu-whole", type=int, default=0, help=argparse.SUPPRESS)
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed (PCIe-inclusive) leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-dispatch roofline replay")
+    ap.add_argument("--no-host-fed", action="store_true", help="--full: skip the host-fed (PCIe-inclusive) leg")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs that put the other single-GPU BASELINE workloads (infer_base = configs[4], "
-                         "base_recipe_hubert = configs[3] on one GPU) into config.other_configs of the default line")
+                    help="--full: skip the short legs that put the other single-GPU BASELINE workloads (infer_base = configs[4], "
+                         "base_recipe_hubert = configs[3] on one GPU) into config.other_configs of the line")
     ap.add_argument("--grad-exchange-dtype", default="fp32", choices=["fp32", "bf16"],
                     help="N > 1: type the gradient ranges are all-reduced in (runtime/distributed.py; fp32 = the reference's)")
     ap.add_argument("--exchange-proxy", default=None, metavar="WGS,RANKS,GBPS",
@@ -802,7 +817,7 @@ def main():
     # reference).  Steady state: the clock starts once the prefetcher's queue is full.  Reported in `config`
     # (host_fed_ms_per_step), never as `value`.
     host_fed = None
-    if not args.no_host_fed and world == 1:
+    if args.full and not args.no_host_fed and world == 1:
         n_h = args.steps
         feed = [samples[i] for i in range(args.warmup, args.warmup + n_h)]
         pf = prefetch.DevicePrefetcher(feed, eng, depth=3, model=model if hub else None)
@@ -818,7 +833,7 @@ def main():
         host_fed = th / n_h * 1e3
         vlog('host-fed (PCIe-inclusive), prefetched uploads: %.3f ms/step, %.0f mel-frames/s over %d steps' % (
             host_fed, sum(frames[args.warmup:args.warmup + n_h]) / th, n_h))
-    if os.environ.get('S2ST_BENCH_VERBOSE'):
+    if args.full and os.environ.get('S2ST_BENCH_VERBOSE'):
         n_h = min(args.steps, 10)
         feed = [samples[i] for i in range(args.warmup, args.warmup + n_h)]
         torch.cuda.synchronize()
@@ -863,12 +878,12 @@ def main():
     # of this command reports (profiles/r02_*_kernel_stats.txt) -- so per-kernel sums cannot exceed the step.
     roofline = None
     n_replay = args.steps
-    if not args.no_roofline and world > 1 and rank != 0:
+    if args.full and not args.no_roofline and world > 1 and rank != 0:
         # the replay below contains the gradient all-reduce: every rank has to take the same steps
         for i in range(args.warmup, args.warmup + n_replay):
             step(i)
         torch.cuda.synchronize()
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         import ctypes as C
         lib = bd.lib()
         lib.s2st_profile_enable.argtypes = [C.c_int32]
@@ -1015,7 +1030,7 @@ def main():
     # ---- CPU baseline leg: the oracle (torch fp32, all usable host cores) on one timed batch, in a child process
     #      with a hard time limit so a slow host can never stall the bench ----------------------------------------
     cpu = None
-    if args.cpu_seconds > 0 and rank == 0 and world == 1:
+    if args.full and args.cpu_seconds > 0 and rank == 0 and world == 1:
         import subprocess
         n_cpu = args.cpu_utts or (8 if hub else 0)
         ids = mine[args.warmup] if n_cpu <= 0 else mine[args.warmup][:n_cpu]
@@ -1042,7 +1057,7 @@ def main():
     profiled = any(("rocprof" in os.environ.get(k, "").lower()) for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB",
                                                                           "ROCPROFILER_LIBRARY_PATH")) or \
         any(k.startswith(("ROCPROF_", "ROCPROFILER_")) for k in os.environ)
-    if rank == 0 and world == 1 and args.config == "base_recipe" and not args.no_other_configs and not profiled:
+    if args.full and rank == 0 and world == 1 and args.config == "base_recipe" and not args.no_other_configs and not profiled:
         import subprocess
         others = {}
         legs = {"infer_base": ["--config", "infer_base", "--steps", "8", "--warmup", "2", "--cpu-seconds", "0", "--no-roofline"],
@@ -1051,7 +1066,7 @@ def main():
         torch.cuda.empty_cache()
         for name, extra in legs.items():
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-other-configs"] + extra,
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-other-configs"] + extra,
                                    capture_output=True, text=True, timeout=600)
                 got = None
                 for ln in r.stdout.splitlines():

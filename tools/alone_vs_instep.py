@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(env):
     e = dict(os.environ, S2ST_BENCH_VERBOSE="1", **env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-other-configs",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full", "--no-other-configs",
                         "--cpu-seconds", "0", "--no-host-fed"] + sys.argv[1:], env=e, capture_output=True, text=True)
     rows, ms = {}, None
     for ln in r.stderr.splitlines():

@@ -10,7 +10,7 @@ done
 for v in default a b ab; do
   if [ $v = default ]; then L=$C/libs2st_hip.so; else L=$C/libs2st_hip_dma_$v.so; fi
   echo "==== kernel table, $v"
-  S2ST_HIP_LIB=$L S2ST_BENCH_VERBOSE=1 python bench.py --steps 20 --warmup 5 --no-other-configs 2>&1 | grep -E "launches .* avg" | head -24
+  S2ST_HIP_LIB=$L S2ST_BENCH_VERBOSE=1 python bench.py --steps 20 --warmup 5 --full --no-other-configs 2>&1 | grep -E "launches .* avg" | head -24
 done
 echo "==== gradient-norm pass with nt loads (Adam nt in both)"
 for rep in 1 2 3; do

@@ -9,13 +9,13 @@ TAG=$1; shift
 O=gpurun_out
 CFG=base_recipe
 for a in "$@"; do if [ "$prev" = "--config" ]; then CFG=$a; fi; prev=$a; done
-S2ST_BENCH_VERBOSE=1 python3 bench.py --steps 20 --warmup 5 "$@" > $O/${TAG}_bench_verbose.txt 2>&1
+S2ST_BENCH_VERBOSE=1 python3 bench.py --steps 20 --warmup 5 --full "$@" > $O/${TAG}_bench_verbose.txt 2>&1
 grep '^{' $O/${TAG}_bench_verbose.txt > $O/${TAG}_bench_line.txt
 # steps the profiled command executes: training configs 5 warm-up + 20 timed + 20 replayed (the host-fed leg is switched off
 # under the profiler); infer_base 5 + 20 timed + 20 with the device's phase generator + decode / vocoder split + roofline pass
 NSTEPS=45; HF=--no-host-fed
 if [ "$CFG" = "infer_base" ]; then NSTEPS=48; HF=; fi
-rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o run -- python3 bench.py --no-other-configs --steps 20 --warmup 5 --cpu-seconds 0 $HF "$@" > $O/prof_$TAG.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o run -- python3 bench.py --full --no-other-configs --steps 20 --warmup 5 --cpu-seconds 0 $HF "$@" > $O/prof_$TAG.log 2>&1
 grep '^{' $O/prof_$TAG.log > $O/${TAG}_bench_line_under_rocprof.txt
 python3 tools/prof_summary.py $O/prof_$TAG/run_results.db $NSTEPS > $O/${TAG}_kernel_stats.txt
 python3 tools/prof_summary.py $O/prof_$TAG/run_results.db 20 last 20 > $O/${TAG}_kernel_stats_replayed_steps.txt   # the launches behind the bench line's roofline

@@ -6,6 +6,6 @@ line() { python -c "import sys,json; d=json.loads(sys.stdin.read()); c=d['config
 for it in 64 8; do
 for ch in 1 2 3; do
   echo "== GL iterations $it, chains $ch" >> $OUT
-  S2ST_BENCH_GL_ITERS=$it S2ST_DECODE_CHAINS=$ch timeout 600 python bench.py --config infer_base --no-other-configs 2>&1 | tail -1 | line >> $OUT 2>&1
+  S2ST_BENCH_GL_ITERS=$it S2ST_DECODE_CHAINS=$ch timeout 600 python bench.py --config infer_base --full --no-other-configs 2>&1 | tail -1 | line >> $OUT 2>&1
 done
 done
