@@ -615,6 +615,34 @@ int s2st_engine_aux_inc_step(s2st_engine* e, int32_t which, int32_t step, const 
                              const int32_t* positions, const float* pe, float* logits_out, float* workspace,
                              int64_t workspace_floats, void* stream);
 
+/* The search itself on the device (csrc/beam_search.hip): what fairseq's SequenceGenerator._generate (:330-571),
+ * search.BeamSearch.step and finalize_hypos do between two decoder steps -- masks (EOS below min_len, NaN, pad, unk penalty,
+ * EOS only at max_len), candidate score = lprob + cumulative score (one fp32 add; beam 0 only at step 0), the top
+ * min(2 beam, beam V - 1) of a sentence's beam x V candidates in the order (value descending, flat index ascending), the EOS
+ * candidates among the first `beam` ranks appended to the sentence's finalised list, and the first `beam` entries of the stable
+ * order of (eos_mask, rank) as the hypotheses the next step continues.  One workgroup per sentence; finished sentences stay in
+ * the batch and are ignored.  beam <= 16, V >= 2 (S2ST_ERR_SHAPE otherwise: the caller then searches on the host).
+ * state: caller-owned, s2st_beam_state_bytes bytes of 32-bit words (R = bsz beam, L1 = max_len + 1):
+ *   header [16]: word 0 = number of finished sentences, words 4 .. 8 = pad, unk, eos, min_len, unk_penalty (float bits);
+ *   finished [bsz] | n_final [bsz] | ignore [R] (cands_to_ignore) | final_step [R] | final_score [R] (fp32, the raw EOS score)
+ *   | final_tokens [R][L1] | final_scores [R][L1] (fp32, cumulative; record j of sentence s is row s beam + j, its first
+ *   final_step + 1 entries hold the token prefix ending in EOS and the score history ending in the EOS score)
+ *   -- the header and these arrays are the RESULT BLOCK, s2st_beam_result_bytes bytes from the start of the state --
+ *   | tokens [2][R][L1 + 1] | scores [2][R][L1] (fp32): the hypotheses' histories, double-buffered: step s gathers the surviving
+ *   hypotheses' rows from copy s & 1 into copy (s + 1) & 1.
+ * begin: zeroes the state, stores the constants, tokens[0][:][0] = eos.  step s (s = 0, 1, ..): lprobs [R][V] of the hypotheses'
+ * last tokens; tokens_next_out [R] (int64) and reorder_out [R] (int32) feed s2st_engine_aux_inc_step of step s + 1 as they are.
+ * fetch / poll: asynchronous copies of the result block / of the header to caller-owned (pinned) host memory.  Nothing here
+ * allocates or synchronises. */
+int64_t s2st_beam_state_bytes(int32_t bsz, int32_t beam, int32_t max_len);
+int64_t s2st_beam_result_bytes(int32_t bsz, int32_t beam, int32_t max_len);
+int s2st_beam_begin(void* state, int32_t bsz, int32_t beam, int32_t max_len, int32_t pad, int32_t unk, int32_t eos,
+                    int32_t min_len, float unk_penalty, void* stream);
+int s2st_beam_step(void* state, int32_t bsz, int32_t beam, int32_t max_len, const float* lprobs, int32_t V, int32_t step,
+                   int64_t* tokens_next_out, int32_t* reorder_out, void* stream);
+int s2st_beam_fetch(const void* state, int32_t bsz, int32_t beam, int32_t max_len, void* host_out, void* stream);
+int s2st_beam_poll(const void* state, void* host_out_64_bytes, void* stream);
+
 /* ---- frozen HuBERT front end of config 4 (--use-hubert): fairseq/models/hubert/hubert.py:412-461,
  * 518-534 (extract_features, eval, mask=False) with wav2vec2.py:736-905.  The handle is an
  * s2st_engine in "hubert mode": parameters are enumerated / bound with s2st_engine_param_info,

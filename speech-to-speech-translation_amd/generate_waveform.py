@@ -132,6 +132,44 @@ def dump_result(args, vocoder_name: str, sample_rate: int, sample_id, hypo, writ
                  lambda p: write_wav(p, _to_np(hypo["targ_waveform"]), sample_rate))
 
 
+def load_task_model_dataset(args, device, configure=None, on_model_built=None):
+    """What the generation scripts share (generate_waveform.py:134-147, fairseq_cli/generate_for_s2st.py:83-114): the
+    checkpoint in the reference's ``.pt`` layout, the task set up from the command line with the checkpoint's model flags
+    (``configure(margs)`` applies the script's own generation-time flags), the model with the checkpoint's tensors, the
+    split.  Returns (task, model, margs, dataset)."""
+    from . import criterions, models, tasks  # noqa: F401  (fill the registries)
+    state = checkpoint_utils.load_checkpoint_to_cpu(args.path)
+    margs = state["cfg"]["model"]
+    margs = argparse.Namespace(**(vars(margs) if not isinstance(margs, dict) else margs))
+    # generation-time flags override what the checkpoint carried (checkpoint_utils.load_model_ensemble_and_task +
+    # generate_waveform.py:142-144: the task is set up from the command line, n_frames_per_step from the checkpoint)
+    margs.data, margs.config_yaml = args.data, args.config_yaml
+    margs.precise_gemm = bool(args.precise_gemm)
+    margs.eval_inference = False
+    margs.train_subset = None
+    if configure is not None:
+        configure(margs)
+    for k in ("load_pretrained_encoder_from", "load_pretrained_decoder_from"):
+        setattr(margs, k, None)  # the tensors come from the checkpoint itself
+    task = TASKS[getattr(margs, "task", None) or args.task].setup_task(margs, device=device)
+    if task.data_cfg is not None:
+        margs.src_vocab_size, margs.tgt_vocab_size = len(task.source_dictionary), len(task.target_dictionary)
+    model = task.build_model(margs)
+    model.load_state_dict(state["model"], strict=True)
+    if on_model_built is not None:
+        on_model_built(model)
+    dataset = task.load_dataset(args.gen_subset)
+    return task, model, margs, dataset
+
+
+def batch_iterator(task, dataset, args):
+    """Length-ordered max-tokens batches of the split, no shuffle (generate_waveform.py:160-170)."""
+    return task.get_batch_iterator(dataset, max_tokens=args.max_tokens, max_sentences=args.batch_size,
+                                   max_positions=(sys.maxsize, sys.maxsize),
+                                   required_batch_size_multiple=args.required_batch_size_multiple, seed=args.seed,
+                                   num_shards=args.num_shards, shard_id=args.shard_id).next_epoch_itr(shuffle=False)
+
+
 def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None, on_model_built=None,
          parser: Optional[argparse.ArgumentParser] = None, mtl: bool = False) -> Dict:
     """``mtl``: the flow of generate_waveform_mtl.py (see generate_waveform_mtl.py in this package): the task's own
@@ -148,32 +186,15 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         if not torch.cuda.is_available():
             raise SystemExit("s2st_amd.generate_waveform needs a HIP device (the product path has no CPU fallback)")
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
-    from . import criterions, models, tasks  # noqa: F401  (fill the registries)
-    state = checkpoint_utils.load_checkpoint_to_cpu(args.path)
-    margs = state["cfg"]["model"]
-    margs = argparse.Namespace(**(vars(margs) if not isinstance(margs, dict) else margs))
-    # generation-time flags override what the checkpoint carried (checkpoint_utils.load_model_ensemble_and_task +
-    # generate_waveform.py:142-144: the task is set up from the command line, n_frames_per_step from the checkpoint)
-    margs.data, margs.config_yaml = args.data, args.config_yaml
-    margs.eos_prob_threshold = args.eos_prob_threshold
-    margs.spec_bwd_max_iter = args.spec_bwd_max_iter
-    margs.gl_phase_rng = args.gl_phase_rng
-    margs.vocoder = args.vocoder
-    margs.precise_gemm = bool(args.precise_gemm)
-    margs.eval_inference = False
-    margs.train_subset = None
-    if args.max_target_positions is not None:
-        margs.max_target_positions = args.max_target_positions
-    for k in ("load_pretrained_encoder_from", "load_pretrained_decoder_from"):
-        setattr(margs, k, None)  # the tensors come from the checkpoint itself
-    task = TASKS[getattr(margs, "task", None) or args.task].setup_task(margs, device=device)
-    if task.data_cfg is not None:
-        margs.src_vocab_size, margs.tgt_vocab_size = len(task.source_dictionary), len(task.target_dictionary)
-    model = task.build_model(margs)
-    model.load_state_dict(state["model"], strict=True)
-    if on_model_built is not None:
-        on_model_built(model)
-    dataset = task.load_dataset(args.gen_subset)
+    def configure(margs):
+        margs.eos_prob_threshold = args.eos_prob_threshold
+        margs.spec_bwd_max_iter = args.spec_bwd_max_iter
+        margs.gl_phase_rng = args.gl_phase_rng
+        margs.vocoder = args.vocoder
+        if args.max_target_positions is not None:
+            margs.max_target_positions = args.max_target_positions
+
+    task, model, margs, dataset = load_task_model_dataset(args, device, configure, on_model_built)
     sample_rate = task.sr
     if args.output_sample_rate not in (None, sample_rate):
         raise SystemExit(f"--output-sample-rate {args.output_sample_rate}: resampling (torchaudio sox effects in the "
@@ -187,10 +208,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         Path(args.results_path).mkdir(exist_ok=True, parents=True)
         src_f = open(os.path.join(args.results_path, "src_texts.txt"), "w")
         hyp_f = open(os.path.join(args.results_path, "hyps_src_texts.txt"), "w")
-    itr = task.get_batch_iterator(dataset, max_tokens=args.max_tokens, max_sentences=args.batch_size,
-                                  max_positions=(sys.maxsize, sys.maxsize),
-                                  required_batch_size_multiple=args.required_batch_size_multiple, seed=args.seed,
-                                  num_shards=args.num_shards, shard_id=args.shard_id).next_epoch_itr(shuffle=False)
+    itr = batch_iterator(task, dataset, args)
     Path(args.results_path).mkdir(exist_ok=True, parents=True)
     ids = getattr(dataset, "ids", None)
     written: List[str] = []

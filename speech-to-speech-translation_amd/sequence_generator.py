@@ -12,6 +12,14 @@ fairseq/sequence_generator.py:330-400): ``s2st_engine_aux_inc_begin`` projects t
 values once, ``s2st_engine_aux_inc_step`` embeds the hypotheses' last tokens, appends their key / value rows to the caches and
 attends over them, and the surviving beams' indices reorder the caches on the device -- a hypothesis costs O(L) per step.
 ``incremental=False`` keeps rounds 2 - 5's form (the decoder re-run on the whole prefix each step): the reference result either way.
+
+``search="device"`` (with ``incremental=True``) keeps the search itself on the device as well: ``s2st_beam_step``
+(csrc/beam_search.hip) does the masks, the top-2k selection, the EOS / finalise / active-hypothesis bookkeeping and the re-gather
+of the histories of one step, and hands the next tokens and the reorder vector to ``s2st_engine_aux_inc_step`` as device
+pointers.  The host reads the count of finished sentences every ``poll_every`` steps and the finalised records once after the
+loop; the length normalisation, the positional-score differencing and the final sort are the host form's numpy expressions
+applied to those records, so tokens are equal and scores are equal bit for bit.  ``search="host"`` (the default) is the form above.
+``last_d2h_copies`` counts the device-to-host copies of the last ``generate`` call in either form.
 """
 from __future__ import annotations
 
@@ -25,15 +33,29 @@ import torch
 from .runtime import binding as bd
 from .runtime.engine import PAD
 
+DEVICE_MAX_BEAM = 16  # (s2st_beam_step's lanes keep 2 x beam candidates in registers; wider beams search on the host)
+# How often the device form reads the finished-sentence count back.  From profiles/aux_decode_rate.txt: a poll costs ~17 us;
+# at 8 a step is within 1.5 % of the no-poll floor and a batch that ends early runs at most 7 idle steps past its end.
+DEFAULT_POLL_EVERY = 8
+
 
 class AuxSequenceGenerator:
     def __init__(self, model, tgt_dict, which: str = "st", beam_size: int = 5, max_len_a: float = 0.0, max_len_b: int = 200,
                  max_len: int = 0, min_len: int = 1, normalize_scores: bool = True, len_penalty: float = 1.0,
-                 unk_penalty: float = 0.0, temperature: float = 1.0, incremental: bool = True, **unused):
+                 unk_penalty: float = 0.0, temperature: float = 1.0, incremental: bool = True, search: str = "host",
+                 poll_every: int = DEFAULT_POLL_EVERY, **unused):
         if which not in ("asr", "st"):
             raise ValueError("which must be 'asr' or 'st'")
         if temperature != 1.0:
             raise NotImplementedError("temperature != 1")
+        if search not in ("host", "device"):
+            raise ValueError("search must be 'host' or 'device'")
+        if search == "device" and not incremental:
+            raise ValueError("search='device' needs incremental=True (the step-by-step decoder with key / value caches)")
+        if poll_every < 1:
+            raise ValueError("poll_every must be >= 1")
+        self.search, self.poll_every = search, int(poll_every)
+        self.last_d2h_copies = self.last_steps = 0
         self.model, self.which, self.tgt_dict = model, which, tgt_dict
         self.incremental = bool(incremental)
         self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
@@ -70,6 +92,7 @@ class AuxSequenceGenerator:
         last = logits[:, L - 1, :].contiguous()
         lp = torch.empty(Bb, V, dtype=torch.float32, device=dev)
         bd.call("s2st_log_softmax_rows_f32", last, V, lp, V, Bb, V, 1)  # get_normalized_probs(log_probs=True)
+        self.last_d2h_copies += 1
         return lp.cpu().numpy()
 
     # -- the incremental form: caches live in a device buffer owned here for the length of one generate() ----------------
@@ -102,6 +125,7 @@ class AuxSequenceGenerator:
                                                   inc["pe"].data_ptr(), inc["logits"].data_ptr(), eng.workspace.data_ptr(),
                                                   eng.workspace.numel(), bd.stream_ptr()), "s2st_engine_aux_inc_step")
         bd.call("s2st_log_softmax_rows_f32", inc["logits"], V, inc["lp"], V, Bb, V, 1)  # get_normalized_probs(log_probs=True)
+        self.last_d2h_copies += 1
         return inc["lp"].cpu().numpy()
 
     @torch.no_grad()
@@ -109,6 +133,7 @@ class AuxSequenceGenerator:
         model = models[0] if isinstance(models, (list, tuple)) else models
         assert model is self.model
         model.eval()
+        self.last_d2h_copies = self.last_steps = 0
         ni = sample["net_input"]
         enc = model.forward_encoder(ni.get("src_speech"), ni.get("src_speech_lens"), ni.get("collated_audios_orig"),
                                     ni.get("padding_mask"))
@@ -130,6 +155,10 @@ class AuxSequenceGenerator:
         src_len = int(src.shape[1]) if src is not None else int(ni["collated_audios_orig"].shape[1])
         max_len = min(int(self.max_len_a * src_len + self.max_len_b), self.max_len - 1)
         assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
+        if self.search == "device" and beam <= DEVICE_MAX_BEAM:
+            if not self.incremental:
+                raise ValueError("search='device' needs incremental=True")
+            return self._generate_device(tap_b, lens_b, E, bsz, beam, max_len)
 
         ninf = np.float32(-math.inf)
         scores = np.zeros((bsz * beam, max_len + 1), dtype=np.float32)
@@ -185,6 +214,7 @@ class AuxSequenceGenerator:
                 eos_bbsz_idx = cand_bbsz_idx[:, :beam][sel]
                 eos_scores = cand_scores[:, :beam][sel].copy()
                 self._finalize(step, eos_bbsz_idx, eos_scores, tokens, scores, finalized, finished, beam, max_len)
+            self.last_steps = step + 1
             if all(finished):
                 break
             assert step < max_len, f"{step} < {max_len}"
@@ -206,6 +236,76 @@ class AuxSequenceGenerator:
         return [[{"tokens": torch.from_numpy(h["tokens"]), "score": torch.tensor(h["score"]),
                   "positional_scores": torch.from_numpy(h["positional_scores"]), "attention": torch.empty(0),
                   "alignment": torch.empty(0)} for h in hs] for hs in finalized]
+
+    def _generate_device(self, tap_b, lens_b, E: int, bsz: int, beam: int, max_len: int) -> List[List[Dict]]:
+        """The loop with the search on the device: per step one decoder step, one log-softmax, one s2st_beam_step, all on
+        the current stream; nothing crosses to the host but the finished-sentence count every ``poll_every`` steps."""
+        eng, dev = self.model.engine, self.model.engine.device
+        on_gpu = dev.type == "cuda"
+        V, R, L1 = self.vocab_size, bsz * beam, max_len + 1
+        lib = bd.lib()
+        nbytes, rbytes = int(lib.s2st_beam_state_bytes(bsz, beam, max_len)), int(lib.s2st_beam_result_bytes(bsz, beam, max_len))
+        if nbytes < 0 or rbytes < 0:
+            raise bd.S2STHipError(f"s2st_beam_state_bytes / _result_bytes failed ({nbytes}, {rbytes})")
+        state = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+        result = torch.empty(rbytes // 4, dtype=torch.int32, pin_memory=on_gpu)
+        header = torch.zeros(16, dtype=torch.int32, pin_memory=on_gpu)
+        bd.call("s2st_beam_begin", state, bsz, beam, max_len, self.pad, self.unk, self.eos, int(self.min_len),
+                float(self.unk_penalty))
+        inc = self._inc_begin(tap_b, lens_b, E, max_len)
+        tok = torch.full((R,), self.eos, dtype=torch.int64, device=dev)
+        reorder = torch.zeros(R, dtype=torch.int32, device=dev)
+        # make_positions: no padding inside a prefix, every hypothesis sits at step + PAD + 1
+        pos = (torch.arange(L1, dtype=torch.int32, device=dev) + (PAD + 1))[:, None].expand(L1, R).contiguous()
+        event = torch.cuda.Event() if on_gpu else None
+        for step in range(max_len + 1):
+            bd.check(lib.s2st_engine_aux_inc_step(eng.h, inc["w"], step, tok.data_ptr(), reorder.data_ptr() if step else None,
+                                                  pos[step].data_ptr(), inc["pe"].data_ptr(), inc["logits"].data_ptr(),
+                                                  eng.workspace.data_ptr(), eng.workspace.numel(), bd.stream_ptr()),
+                     "s2st_engine_aux_inc_step")
+            bd.call("s2st_log_softmax_rows_f32", inc["logits"], V, inc["lp"], V, R, V, 1)  # get_normalized_probs(log_probs=True)
+            bd.call("s2st_beam_step", state, bsz, beam, max_len, inc["lp"], V, step, tok, reorder)
+            self.last_steps = step + 1
+            if step < max_len and (step + 1) % self.poll_every == 0:
+                bd.check(lib.s2st_beam_poll(state.data_ptr(), header.data_ptr(), bd.stream_ptr()), "s2st_beam_poll")
+                self.last_d2h_copies += 1
+                if event is not None:
+                    event.record()
+                    event.synchronize()
+                if int(header[0]) == bsz:
+                    break
+        bd.check(lib.s2st_beam_fetch(state.data_ptr(), bsz, beam, max_len, result.data_ptr(), bd.stream_ptr()), "s2st_beam_fetch")
+        self.last_d2h_copies += 1
+        if event is not None:
+            event.record()
+            event.synchronize()
+        h = result.numpy()
+        o = 16
+        fin, o = h[o:o + bsz], o + bsz
+        n_final, o = h[o:o + bsz], o + bsz
+        o += R  # (cands_to_ignore)
+        final_step, o = h[o:o + R], o + R
+        final_score, o = h[o:o + R].view(np.float32), o + R
+        final_tokens, o = h[o:o + R * L1].reshape(R, L1), o + R * L1
+        final_scores = h[o:o + R * L1].view(np.float32).reshape(R, L1)
+        assert int(h[0]) == bsz and bool(fin.all()), "the search ended with unfinished sentences"
+        finalized: List[List[Dict]] = [[] for _ in range(bsz)]
+        for s in range(bsz):
+            for j in range(int(n_final[s])):  # finalize_hypos' host share (fairseq/sequence_generator.py:607-716), as _finalize
+                row = s * beam + j
+                st = int(final_step[row])
+                pos_scores = final_scores[row, :st + 1].copy()
+                pos_scores[1:] = pos_scores[1:] - pos_scores[:-1]
+                score = final_score[row]
+                if self.normalize_scores:
+                    score = score / np.float32((st + 1) ** self.len_penalty)
+                finalized[s].append({"tokens": final_tokens[row, :st + 1].astype(np.int64), "score": float(score),
+                                     "positional_scores": pos_scores})
+            sc = np.array([x["score"] for x in finalized[s]], dtype=np.float32)
+            finalized[s] = [finalized[s][i] for i in np.argsort(-sc, kind="stable")]
+        return [[{"tokens": torch.from_numpy(x["tokens"]), "score": torch.tensor(x["score"]),
+                  "positional_scores": torch.from_numpy(x["positional_scores"]), "attention": torch.empty(0),
+                  "alignment": torch.empty(0)} for x in hs] for hs in finalized]
 
     def _finalize(self, step, bbsz_idx, eos_scores, tokens, scores, finalized, finished, beam, max_len):
         """fairseq/sequence_generator.py:607-716 (no sentence pruning here, so batch index == sentence index)."""

@@ -206,7 +206,7 @@ class S2ST_TranslationTask(TaskBase):  # fairseq's LegacyFairseqTask when fairse
             beam_size=getattr(args, "beam", 5), max_len_a=getattr(args, "max_len_a", 0),
             max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),
             len_penalty=getattr(args, "lenpen", 1.0), unk_penalty=getattr(args, "unkpen", 0.0),
-            **(extra_gen_cls_kwargs or {}))
+            search=getattr(args, "search", "host"), **(extra_gen_cls_kwargs or {}))
 
     def reduce_metrics(self, logging_outputs, criterion):
         """fairseq/tasks/fairseq_task.py:586-617: the criterion aggregates (s2st_loss.py:350-407)."""
