@@ -429,6 +429,9 @@ int32_t s2st_engine_num_segments(const s2st_engine* e);
  * caller's stream and this stream have drained what was enqueued so far: a gradient all-reduce on
  * another stream must wait on both (the data-path stream itself joins only after the last segment). */
 void* s2st_engine_side_stream(const s2st_engine* e);
+/* Which pieces of S2ST_DEC_OVERLAP the last forward actually put on the second stream (bit 0: the decoder's front issued
+ * ahead of the encoder, bit 1: layer 0's tail of the backward); 0 when the switch, the model or the stream set rules them out. */
+int32_t s2st_engine_dec_overlap_active(const s2st_engine* e);
 /* after segment i has run, gradients in arena range [lo, hi) are final */
 int s2st_engine_segment_range(const s2st_engine* e, int32_t i, int64_t* lo, int64_t* hi);
 /* The optimizer update of the bound arenas (trainer.py:838-873 + adam.py:163-239, as s2st_adam_f32 with zero_grad = 1)

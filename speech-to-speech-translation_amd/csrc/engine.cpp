@@ -97,6 +97,25 @@ struct s2st_engine {
   hipEvent_t ev_auxb_ = nullptr;
   size_t aux_wait_idx = 0, aux_lo_idx = 0, aux_hi_idx = 0;  // tape indices: tap-LN end; aux section [lo, hi)
   bool aux_bwd_on_side = false;
+  // S2ST_DEC_OVERLAP=<bit mask> (per call, default 3; 0 = everything below in tape order on the data path): mel-decoder work
+  // that does not depend on the encoder, or that the encoder's backward does not depend on, runs on the second stream
+  //   bit 0  forward: prenet, positions, layer 0's self-attention block and cross-attention query projection read only
+  //          prev_output_tokens -- issued on the second stream ahead of the encoder (forward(): dec_early)
+  //   bit 1  backward: everything of layer 0 below its cross-attention's dK|dV (query projection ... prenet) produces
+  //          parameter gradients only -- tape range [tail_lo_idx, tail_hi_idx) on the second stream
+  // (A third piece was built and measured: each hoisted K|V projection's backward on the second stream right behind its
+  //  layer's cross-attention.  The data path then has to wait for the encoder output's gradient behind the second stream's
+  //  backlog of weight-gradient products, ~0.75 ms at that point of the step: +0.26 ms per step, left out --
+  //  profiles/r07_dec_overlap_pieces_ab.txt.)
+  int dec_overlap = 3;
+  hipEvent_t ev_head_ = nullptr;    // the block issued ahead (bit 0) is complete
+  // every event of the second stream was created (by the calls' results, not by the handles: the CPU emulator's events are
+  // null handles, and S2ST_DEC_OVERLAP has to engage there for tests/test_decoder_overlap.py to check its re-ordering)
+  bool side_events_ = false;
+  size_t tail_lo_idx = 0, tail_hi_idx = 0;
+  bool tail_bwd_on_side = false, tail_side_ = false;  // tail_side_: st_ points at the second stream for the tail's closures
+  bool dec_early_active = false;    // the last forward issued the block ahead, on the second stream (s2st_engine_dec_overlap_active)
+  size_t xattn0_idx = 0;            // tape index of the closure of mel-decoder layer 0's cross-attention (0: none)
   bool side_used = false;
   float* skws_side = nullptr;
   bool side_allowed = false;  // bf16-operand mode and no S2ST_NO_SIDE_STREAM=1
@@ -109,7 +128,15 @@ struct s2st_engine {
     int pr_least = 0, pr_greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest) != hipSuccess) pr_least = 0;
     if (hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, pr_least) != hipSuccess) side_ = nullptr;
-    if (side_ && hipEventCreateWithFlags(&ev_kv_, hipEventDisableTiming) != hipSuccess) ev_kv_ = nullptr;
+    // No stream priorities: a plain second stream carries the same schedule.  This is also what gives the CPU emulator
+    // (tests/hipemu: its priority form always fails) a second stream at all -- a label there, every launch is synchronous --
+    // so the emulator suite now walks the second-stream schedule (aux heads, hoisted K|V projections, weight-gradient forks,
+    // S2ST_DEC_OVERLAP) in its issue order instead of the one-stream one.  Not next to the two-chain mode's own stream: the
+    // emulator hands out ONE stream handle, and a second stream equal to chain1_ would be taken for it (ws_for, chain_count).
+    if (!side_ && !chain1_ && hipStreamCreateWithFlags(&side_, hipStreamNonBlocking) != hipSuccess) side_ = nullptr;
+    bool ev_ok = side_ != nullptr;
+    if (side_ && hipEventCreateWithFlags(&ev_kv_, hipEventDisableTiming) != hipSuccess) { ev_kv_ = nullptr; ev_ok = false; }
+    if (side_ && hipEventCreateWithFlags(&ev_head_, hipEventDisableTiming) != hipSuccess) { ev_head_ = nullptr; ev_ok = false; }
     if (side_ && (hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming) != hipSuccess ||
                   hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming) != hipSuccess ||
                   hipEventCreateWithFlags(&ev_taps_, hipEventDisableTiming) != hipSuccess ||
@@ -117,6 +144,7 @@ struct s2st_engine {
       hipStreamDestroy(side_);
       side_ = nullptr;
     }
+    side_events_ = side_ && ev_ok;
   }
   hipStream_t fork_side() {  // everything issued on st_ so far happens-before what follows on the returned stream
     if (!side_) { sync_chains(); return st_; }
@@ -445,6 +473,7 @@ void s2st_engine_destroy(s2st_engine* e) {
     if (e->ev_taps_) hipEventDestroy(e->ev_taps_);
     if (e->ev_auxb_) hipEventDestroy(e->ev_auxb_);
     if (e->ev_kv_) hipEventDestroy(e->ev_kv_);
+    if (e->ev_head_) hipEventDestroy(e->ev_head_);
     for (hipEvent_t ev : e->adam_ev) hipEventDestroy(ev);
   }
   if (e->chain1_) {
@@ -595,6 +624,10 @@ int s2st_engine_wait_optimizer(s2st_engine* e, void* stream) {
 
 int32_t s2st_engine_num_segments(const s2st_engine* e) { return e->n_segments(); }
 
+int32_t s2st_engine_dec_overlap_active(const s2st_engine* e) {
+  return e ? (e->dec_early_active ? 1 : 0) | (e->tail_bwd_on_side ? 2 : 0) : 0;
+}
+
 void* s2st_engine_side_stream(const s2st_engine* e) {  // (a trainer asks before the first forward: made on demand)
   const_cast<s2st_engine*>(e)->ensure_side();
   return (void*)e->side_;
@@ -628,6 +661,7 @@ int s2st_engine_decode_begin(s2st_engine* e, const s2st_batch* b, const s2st_out
   e->bt.tgt = nullptr;
   e->outs = *out;
   e->stop_after_encoder = true;
+  e->adam_wait_all((hipStream_t)stream);  // (the AR steps read every decoder parameter; not left to the per-chunk waits of a forward that stops early)
   int rc = e->forward();
   e->stop_after_encoder = false;
   if (rc) return rc;

@@ -487,10 +487,10 @@
   Ten* cross_kv(Ten* encx, const XAttnP& a, int C) {
     return linear(encx, a.kv_w, a.kv_b, 2 * C, encx->cols, 0, 0.f, nullptr, nullptr, true);
   }
-  Ten* cross_attn_block(Ten* x, Ten* encx, const XAttnP& a, int B, int T, int S, int H,
+  // q: the projected queries (dec_head)
+  Ten* cross_attn_block(Ten* q, Ten* encx, const XAttnP& a, int B, int T, int S, int H,
                         const int* klen, Ten* resid, float* attn_mean_out, Ten* kv_pre = nullptr) {
-    const int C = x->cols;
-    Ten* q = linear(x, a.q_w, a.q_b, C, C, 0, 0.f, nullptr, nullptr, true);
+    const int C = q->cols;
     Ten* kv = kv_pre ? kv_pre : cross_kv(encx, a, C);
     if (kv_pre && kv_wait_) {  // first consumer of the projections issued on the second stream
       wait_traced(st_, ev_kv_, "cross-attention K|V projections");
@@ -499,6 +499,7 @@
     }
     AttnIO io{q, 0, C, kv, 0, 2 * C, kv, C, 2 * C};
     Ten* o = attention(io, B, T, S, H, C / H, klen, 0, bt.training ? c.attn_dropout : 0.f, attn_mean_out);
+    if (kv_pre && !xattn0_idx) xattn0_idx = tape.size() - 1;  // (mel-decoder layer 0: what lies below this closure may leave the data path, backward_segment)
     return linear(o, a.out_w, a.out_b, C, C, 0, bt.training ? c.dropout : 0.f, resid);
   }
   Ten* ffn_block(Ten* x, const LinP& fc1, const LinP& fc2, Ten* resid) {
@@ -517,15 +518,29 @@
     x = layernorm(self_attn_block(x, l.sa, B, T, H, bt.enc_lens, 0, x), l.ln1);
     return layernorm(ffn_block(x, l.fc1, l.fc2, x), l.ln2);
   }
-  Ten* dec_layer(Ten* x, Ten* encx, const DecLayerP& l, int B, int T, int S, int H, bool pre_ln,
-                 const int* self_klen, float* attn_mean_out, Ten* kv_pre = nullptr) {
+  // The part of a decoder layer that does not read the encoder: the self-attention block and the cross-attention's query
+  // projection.  x: the residual stream behind the self-attention block; q: the projected queries.
+  struct DecHead { Ten* x = nullptr; Ten* q = nullptr; };
+  DecHead dec_head(Ten* x, const DecLayerP& l, int B, int T, int H, bool pre_ln, const int* self_klen) {
+    DecHead h;
+    Ten* xn;
     if (pre_ln) {
-      x = self_attn_block(layernorm(x, l.ln1, nullptr, true), l.sa, B, T, H, self_klen, 1, x);
-      x = cross_attn_block(layernorm(x, l.ln2, nullptr, true), encx, l.xa, B, T, S, H, bt.enc_lens, x, attn_mean_out, kv_pre);
-      return ffn_block(layernorm(x, l.ln3, nullptr, true), l.fc1, l.fc2, x);
+      h.x = self_attn_block(layernorm(x, l.ln1, nullptr, true), l.sa, B, T, H, self_klen, 1, x);
+      xn = layernorm(h.x, l.ln2, nullptr, true);
+    } else {
+      h.x = xn = layernorm(self_attn_block(x, l.sa, B, T, H, self_klen, 1, x), l.ln1);
     }
-    x = layernorm(self_attn_block(x, l.sa, B, T, H, self_klen, 1, x), l.ln1);
-    x = layernorm(cross_attn_block(x, encx, l.xa, B, T, S, H, bt.enc_lens, x, attn_mean_out, kv_pre), l.ln2);
+    const int C = xn->cols;
+    h.q = linear(xn, l.xa.q_w, l.xa.q_b, C, C, 0, 0.f, nullptr, nullptr, true);
+    return h;
+  }
+  // head: the layer's dec_head() was issued ahead (x is not read then)
+  Ten* dec_layer(Ten* x, Ten* encx, const DecLayerP& l, int B, int T, int S, int H, bool pre_ln,
+                 const int* self_klen, float* attn_mean_out, Ten* kv_pre = nullptr, const DecHead* head = nullptr) {
+    const DecHead h = head ? *head : dec_head(x, l, B, T, H, pre_ln, self_klen);
+    x = cross_attn_block(h.q, encx, l.xa, B, T, S, H, bt.enc_lens, h.x, attn_mean_out, kv_pre);
+    if (pre_ln) return ffn_block(layernorm(x, l.ln3, nullptr, true), l.fc1, l.fc2, x);
+    x = layernorm(x, l.ln2);
     return layernorm(ffn_block(x, l.fc1, l.fc2, x), l.ln3);
   }
 

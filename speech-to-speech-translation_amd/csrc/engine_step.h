@@ -21,6 +21,8 @@
     err = 0;
     site = 0;
     site_log.clear();
+    xattn0_idx = 0;
+    tail_bwd_on_side = tail_side_ = dec_early_active = false;
     site_ctx[0] = 0;
     param_watermark = 0;
     next_segment = 0;
@@ -72,6 +74,7 @@
     forked_ = false;
     in_region_ = false;
     const bool two_chains = nchains == 2 && chain1_ && tr && fast();  // (training step only; see the note at chain_count)
+    dec_overlap = s2st_env_int("S2ST_DEC_OVERLAP", 3);
 
     // sinusoidal tables come from the host side (cached per dim); conv weight layouts are
     // scratch at the bottom of the workspace
@@ -124,6 +127,71 @@
       hipStream_t main_st = st_;
       if (post_on_side) st_ = fork_side();
       for (auto& pc : post_conv) csp.push_back(conv_scratch(pc, true));
+      st_ = main_st;
+    }
+
+    // ---- S2ST_DEC_OVERLAP bit 0: the decoder's front (prenet, positions) and layer 0 up to the cross-attention's query
+    //      projection read only prev_output_tokens.  They are issued HERE, on the second stream, and run beside the
+    //      encoder layers (behind the optimizer's chunks and the weight transposes, which the stream orders; ahead of the
+    //      hoisted K|V projections, which wait for the encoder).  Everything else keeps its place in program order: the
+    //      block draws the dropout sites it has behind the encoder's (n_enc_sites are reserved; checked where the block
+    //      would run), and its closures, site records and parameter touches are held back and filed at that point, so
+    //      tape, segment marks, segment ranges and the site log are what they are without the overlap.  The data path
+    //      meets the block at an event of its own (ev_head_), before layer 0's cross-attention.  With the block out of the
+    //      way the data path has nothing to do under the hoisted K|V projections any more, so it takes layer 0's itself
+    //      (needed at once) and meets the second stream's five at layer 1's cross-attention.
+    // (kv_on_side below minus live() -- on hardware.  It goes by the events' creation RESULTS, kv_on_side by their handles:
+    //  the emulator's events are null handles, so there the block is issued ahead while all K|V projections stay on the
+    //  data-path label; the emulator checks the block's re-ordered issue, the layer-0 / layers-1.. split only runs on a GPU.)
+    const bool kv_side_ok = side_ && side_events_ && hoist_kv && !stop_after_encoder;
+    const bool dec_early = tr && fm && (dec_overlap & 1) && kv_side_ok && !two_chains && !c.text_input && !c.s2t_mode &&
+                           c.dec_layers > 0 && bt.prev && !(dec_spk >= 0 && bt.speaker);
+    struct {
+      std::vector<std::function<void()>> tape;
+      std::vector<s2st_dropout_site> log;
+      size_t n_front = 0;          // closures of the prenet and the positions (a segment mark follows them)
+      long wm_front = 0, wm_head = 0;
+      uint64_t site_first = 0, site_lo = 0, site_hi = 0;  // encoder's first site - 1; the block's sites are (site_lo, site_hi]
+      Ten* y = nullptr;
+      DecHead head;
+    } early;
+    auto dec_front = [&](Ten* prev) {
+      Ten* h = prev;
+      set_ctx("dec.prenet");
+      for (int i = 0; i < c.prenet_layers; ++i)
+        h = linear(h, prenet[i].w, prenet[i].b, prenet[i].N, prenet[i].K, 1, c.prenet_dropout);
+      h = linear(h, prenet.back().w, prenet.back().b, Cd, c.prenet_dim);
+      set_ctx("dec.pe");
+      return add_pe(h, bt.dec_pos, pe_dec, 1.f, pos_alpha, tr ? c.dropout : 0.f);
+    };
+    if (dec_early) {
+      const int n_enc_sites = (c.dropout > 0.f ? 1 : 0) +
+                              c.enc_layers * ((c.attn_dropout > 0.f ? 1 : 0) + (c.dropout > 0.f ? 2 : 0) + (c.act_dropout > 0.f ? 1 : 0));
+      hipStream_t main_st = st_;
+      const uint64_t site0 = site;
+      const long wm0 = param_watermark;
+      const size_t t0 = tape.size(), l0 = site_log.size();
+      early.site_first = site0;
+      early.site_lo = site = site0 + n_enc_sites;
+      if (live()) { st_ = fork_side(); dec_early_active = st_ == side_; }  // behind the bf16 parameter copy and the caller's inputs
+      Ten* prev = newT(B * D, c.out_dim, const_cast<float*>(bt.prev));
+      prev->needs_grad = false;
+      early.y = dec_front(prev);
+      early.n_front = tape.size() - t0;
+      early.wm_front = param_watermark;
+      set_ctx("dec.L%d", 0);
+      early.head = dec_head(early.y, dec[0], B, D, c.dec_heads, c.dec_pre_ln != 0, bt.tgt_lens);
+      early.wm_head = param_watermark;
+      early.site_hi = site;
+      early.tape.assign(std::make_move_iterator(tape.begin() + t0), std::make_move_iterator(tape.end()));
+      tape.resize(t0);
+      if (tape_aware.size() > t0) tape_aware.resize(t0);
+      early.log.assign(site_log.begin() + l0, site_log.end());
+      site_log.resize(l0);
+      site = site0;
+      param_watermark = wm0;
+      site_ctx[0] = 0;
+      if (live()) hipEventRecord(ev_head_, st_);
       st_ = main_st;
     }
 
@@ -238,15 +306,20 @@
         st_ = side_;
         side_used = true;
       }
-      for (int i = 0; i < c.dec_layers; ++i) xkv[i] = cross_kv(enc_out, dec[i].xa, Cd);
+      for (int i = 0; i < c.dec_layers; ++i) {
+        if (dec_early && i == 0) st_ = main_st;
+        xkv[i] = cross_kv(enc_out, dec[i].xa, Cd);
+        if (dec_early && i == 0 && kv_on_side) st_ = side_;
+      }
       if (kv_on_side) {
         hipEventRecord(ev_kv_, side_);
         st_ = main_st;
-        kv_wait_ = true;
+        kv_wait_ = !dec_early;  // (dec_early: from layer 1 on, below)
       }
       mark();
     }
     // ---- decoder: prenet (dropout always on), alpha * positions, layers ---------------------------
+    tail_lo_idx = tape.size();
     Ten* prev = newT(B * D, c.out_dim, const_cast<float*>(bt.prev));
     prev->needs_grad = false;
     if (dec_spk >= 0 && bt.speaker) {
@@ -267,25 +340,50 @@
       });
       prev = pv;
     }
-    Ten* h = prev;
-    set_ctx("dec.prenet");
-    for (int i = 0; i < c.prenet_layers; ++i)
-      h = linear(h, prenet[i].w, prenet[i].b, prenet[i].N, prenet[i].K, 1, c.prenet_dropout);
-    h = linear(h, prenet.back().w, prenet.back().b, Cd, c.prenet_dim);
-    set_ctx("dec.pe");
-    Ten* y = add_pe(h, bt.dec_pos, pe_dec, 1.f, pos_alpha, tr ? c.dropout : 0.f);
+    Ten* y = nullptr;
+    auto file_early = [&](size_t lo, size_t hi, long wm) {  // closures [lo, hi) of the block issued ahead take their place
+      for (size_t k = lo; k < hi; ++k) tape.push_back(std::move(early.tape[k]));
+      tape_aware.resize(tape.size(), 0);
+      if (wm > param_watermark) param_watermark = wm;
+    };
+    if (dec_early) {
+      if (site != early.site_lo && !err) {
+        // n_enc_sites (above) no longer counts what the encoder's front and layers draw: the block ran with other seeds than
+        // in program order.  Loud, never silently another random function; S2ST_DEC_OVERLAP=2 runs without the reservation.
+        fprintf(stderr, "[s2st] S2ST_DEC_OVERLAP: %llu dropout sites reserved for the encoder, %llu drawn -- update n_enc_sites "
+                        "in forward() (engine_step.h)\n", (unsigned long long)(early.site_lo - early.site_first),
+                (unsigned long long)(site - early.site_first));
+        err = S2ST_ERR_SHAPE;
+      }
+      site = early.site_hi;
+      site_log.insert(site_log.end(), early.log.begin(), early.log.end());
+      y = early.y;
+      file_early(0, early.n_front, early.wm_front);
+      if (live()) wait_traced(st_, ev_head_, "decoder front issued ahead");
+    } else {
+      y = dec_front(prev);
+    }
     mark();
+    if (dec_early) file_early(early.n_front, early.tape.size(), early.wm_head);
     in_region_ = two_chains;  // ---- two chains again: decoder layers, final layer norm, the two output projections
     float* attn_out = nullptr;
     Ten* tap_dec_t = nullptr;
     for (int i = 0; i < c.dec_layers; ++i) {
       float* am = (i == c.dec_layers - 1 && bt.want_attn) ? outs.attn : nullptr;
       set_ctx("dec.L%d", i);
-      y = dec_layer(y, enc_out, dec[i], B, D, E, c.dec_heads, c.dec_pre_ln != 0, bt.tgt_lens, am, xkv[i]);
+      if (dec_early && kv_on_side && i == 1) kv_wait_ = true;
+      y = dec_layer(y, enc_out, dec[i], B, D, E, c.dec_heads, c.dec_pre_ln != 0, bt.tgt_lens, am, xkv[i],
+                    (dec_early && i == 0) ? &early.head : nullptr);
       if (c.has_ctc_tgt && i == c.tap_dec) tap_dec_t = y;  // raw layer output (s2st_transformer_mtl.py:325-327)
       if (i % 2 == 1) mark();
     }
     (void)attn_out;
+    // S2ST_DEC_OVERLAP bit 1: the backward's share (backward_segment).  With the projections hoisted, layer 0's query
+    // projection is the closure right below its cross-attention's.
+    if (tr && kv_side_ok && live() && !two_chains && (dec_overlap & 2) && xattn0_idx > tail_lo_idx) {
+      tail_hi_idx = xattn0_idx;
+      tail_bwd_on_side = true;
+    }
     if (has_dec_ln) y = layernorm(y, dec_ln);
     Ten* feat = linear(y, feat_proj.w, feat_proj.b, c.out_dim, Cd, 0, 0.f, nullptr, outs.feat);
     Ten* eos = linear(y, eos_proj.w, eos_proj.b, 1, Cd, 0, 0.f, nullptr, outs.eos);
@@ -487,6 +585,19 @@
         if (i + 1 == aux_lo_idx && st_ != main_st) { flush_wgrad(); flush_lnfold(); hipEventRecord(ev_auxb_, st_); st_ = main_st; }
         if (i + 1 == aux_wait_idx) wait_traced(main_st, ev_auxb_, "aux decoders' backward (tap gradients)");
       }
+      if (tail_bwd_on_side && live()) {
+        // layer 0 below its cross-attention, positions, prenet (and the speaker row's closure in front of it): parameter
+        // gradients only, nothing the data path reads.  No flush_wgrad / flush_lnfold at the switch, unlike the aux section:
+        // the invariant is that every input of a queued product or fold was produced EITHER on the data path before the
+        // fork_side() below (all data-path closures above the tail ran before it, and none runs until the tail is left) OR on
+        // the second stream itself; and the queues are always launched on the second stream, in its order -- from there
+        // directly while st_ points at it, through another fork_side() once the data path flushes again.  Nothing queued
+        // inside the tail reads what the data path produces after the fork.  The segment-end flush below still runs with
+        // st_ on the second stream, so a segment's range is not reported final before its launches are enqueued.
+        const bool in_tail = i >= tail_lo_idx && i < tail_hi_idx;
+        if (in_tail && st_ == main_st) { st_ = fork_side(); tail_side_ = true; }
+        if (!in_tail && tail_side_) { st_ = main_st; tail_side_ = false; }
+      }
       // (a closure that does not launch per chain itself sees everything the second chain did)
       if (live() && !(i < tape_aware.size() && tape_aware[i])) sync_chains();
       tape[i]();
@@ -494,7 +605,11 @@
     }
     flush_wgrad();  // the segment's gradients are final once its launches are enqueued
     flush_lnfold();
-    if (st_ != main_st) { hipEventRecord(ev_auxb_, st_); st_ = main_st; }
+    if (st_ != main_st) {
+      if (!tail_side_) hipEventRecord(ev_auxb_, st_);
+      st_ = main_st;
+    }
+    tail_side_ = false;
     if (live()) sync_chains();  // (the caller's stream is the one the next segment / the optimizer continues on)
     // The segment's weight gradients live on the second stream.  A caller that overlaps the gradient
     // all-reduce waits on that stream itself (s2st_engine_side_stream); the data path only joins once,

@@ -808,6 +808,10 @@ class Engine:
         p = self.lib.s2st_engine_side_stream(self.h)
         return torch.cuda.ExternalStream(p) if p else None
 
+    def dec_overlap_active(self) -> int:
+        """Pieces of ``S2ST_DEC_OVERLAP`` the last forward put on the second stream (bit 0 forward block, bit 1 backward tail)."""
+        return int(self.lib.s2st_engine_dec_overlap_active(self.h))
+
     def num_segments(self) -> int:
         return int(self.lib.s2st_engine_num_segments(self.h))
 
