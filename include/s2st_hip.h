@@ -691,6 +691,52 @@ int64_t s2st_hifigan_workspace_floats(s2st_engine* e, int32_t B, int32_t T_max);
 int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames, int32_t B, int32_t T, float* wave_out,
                          float* workspace, int64_t workspace_floats, void* stream);
 
+/* ---- wav2vec 2.0 CTC recogniser (ASR-BLEU scoring of generated speech): what examples/s2s_trans/evalute_s2s_bleu.py runs
+ * through transformers -- Wav2Vec2Processor's zero-mean / unit-variance normalisation, Wav2Vec2ForCTC (feat_extract_norm
+ * "layer", do_stable_layer_norm: conv + bias -> LayerNorm over channels -> GELU seven times, LayerNorm -> projection,
+ * x += GELU(pos_conv(x)), pre-LN transformer layers, final LayerNorm, lm_head), torch.argmax and the CTC tokenizer's
+ * collapse.  The handle is an s2st_engine in "w2v_ctc mode": parameters are enumerated / bound with
+ * s2st_engine_param_info, s2st_engine_bind(params, NULL, NULL) and s2st_engine_bind_bf16 under the transformers
+ * state_dict names; conv weights are stored [O][k][I] and the weight-normed pos_conv as its effective weight
+ * [G][E/G][k][E/G] (the host wrapper converts).  Forward only. */
+typedef struct {
+  int32_t n_conv;
+  int32_t conv_dim[8], conv_k[8], conv_stride[8];
+  int32_t embed, layers, heads, ffn, conv_pos, conv_pos_groups;
+  int32_t precise;
+  int32_t vocab;                  /* rows of lm_head */
+} s2st_w2v_ctc_config;
+int s2st_w2v_ctc_create(const s2st_w2v_ctc_config* cfg, s2st_engine** out);
+/* frames of n valid samples: floor((n - k) / s) + 1 layer by layer (_get_feat_extract_output_lengths); 0 when too short */
+int32_t s2st_w2v_ctc_out_frames(const s2st_engine* e, int32_t n_samples);
+int64_t s2st_w2v_ctc_workspace_floats(s2st_engine* e, int32_t B, int32_t N);
+/* wave [B][N] fp32 raw samples (whatever lies behind sample_lens[b] is ignored), sample_lens [B], frame_lens [B] =
+ * s2st_w2v_ctc_out_frames(sample_lens[b]), blank = the CTC blank (pad_token_id) -> logits_out [B][T][vocab] with
+ * T = out_frames(N) (rows >= frame_lens[b] are not meaningful), ids_out [B][T] int32 = the collapsed token ids of the valid
+ * frames (-1 behind the count), counts_out [B].  Replaces processor(...), model(...).logits, torch.argmax and the
+ * tokenizer's grouping in evalute_s2s_bleu.py; only valid frames are decoded (the reference also decodes a short
+ * utterance's padded frames). */
+int s2st_w2v_ctc_forward(s2st_engine* e, const float* wave, const int32_t* sample_lens, const int32_t* frame_lens, int32_t B,
+                         int32_t N, int32_t blank, float* logits_out, int32_t* ids_out, int32_t* counts_out,
+                         float* workspace, int64_t workspace_floats, void* stream);
+/* The recogniser's non-GEMM kernels on their own (csrc/w2v_ctc.hip).
+ * s2st_w2v_wave_norm_f32: y[b][i] = (x[b][i] - mean_b) / sqrt(var_b + eps) over the lens[b] valid samples, 0 behind
+ *   (Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm + padding).
+ * s2st_w2v_conv0_ln_gelu_f32: Conv1d(1, C, k, stride, bias) -> LayerNorm(C) -> GELU on wave [B][N] -> y / y_bf16 [B][T][C]
+ *   (either may be NULL), T = (N - k) / stride + 1, C <= 512, k <= 16 (Wav2Vec2LayerNormConvLayer, layer 0).
+ * s2st_w2v_ln_gelu_rows_f32: y[r] = GELU(LayerNorm(x[r])) over rows of C <= 1024, C % 4 == 0 (the same layer behind a
+ *   conv-as-GEMM with the bias in its epilogue); y may be x.
+ * s2st_w2v_ctc_greedy_i32: logits [B][T][V], lens [B] -> ids [B][T], counts [B] (torch.argmax(logits, -1) +
+ *   Wav2Vec2CTCTokenizer.convert_tokens_to_string's grouping, valid frames only; ties go to the lowest id). */
+int s2st_w2v_wave_norm_f32(const float* x, const int32_t* lens, float* y, int32_t B, int32_t N, float eps, void* stream);
+int s2st_w2v_conv0_ln_gelu_f32(const float* wave, const float* w, const float* bias, const float* gamma, const float* beta, float* y, uint16_t* y_bf16, int32_t B, int32_t N, int32_t T, int32_t C, int32_t k, int32_t stride, float eps, void* stream);
+int s2st_w2v_ln_gelu_rows_f32(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y_bf16, int32_t rows, int32_t C, float eps, void* stream);
+int s2st_w2v_ctc_greedy_i32(const float* logits, const int32_t* lens, int32_t* ids, int32_t* counts, int32_t B, int32_t T, int32_t V, int32_t blank, void* stream);
+/* Band-limited resampling by L / M over a ragged batch (replaces librosa.load(path, sr=16000)'s resampling in
+ * evalute_s2s_bleu.py): y[b][t] = sum_d table[(t M) % L][d] x[b][(t M) / L - KL + 1 + d] for t < ceil(n_in[b] L / M), 0
+ * behind; x [B][N_in], y [B][N_out], table [L][KW] = the windowed-sinc filter of every phase (host, float64 -> fp32). */
+int s2st_resample_sinc_f32(const float* x, const int32_t* n_in, const float* table, float* y, int32_t B, int32_t N_in, int32_t N_out, int32_t L, int32_t M, int32_t KL, int32_t KW, void* stream);
+
 /* ======================================================================================
  * Gradient exchange: SUM all-reduce over an RCCL communicator, one process per GPU.  Replaces the bucketed NCCL
  * all-reduce torch DDP runs for the reference (fairseq/models/distributed_fairseq_model.py:58-67); the trainer hands

@@ -295,6 +295,21 @@ int s2st_gemm_streamk_scratch(float* scratch, int64_t floats, void* stream) {
   s2st_gemm_streamk_bind((hipStream_t)stream, scratch, floats);
   return 0;
 }
+int s2st_w2v_wave_norm_f32(const float* x, const int32_t* lens, float* y, int32_t B, int32_t N, float eps, void* stream) {
+  return s2st_w2v_wave_norm(x, lens, y, B, N, eps, (hipStream_t)stream);
+}
+int s2st_w2v_conv0_ln_gelu_f32(const float* wave, const float* w, const float* bias, const float* gamma, const float* beta, float* y, uint16_t* y_bf16, int32_t B, int32_t N, int32_t T, int32_t C, int32_t k, int32_t stride, float eps, void* stream) {
+  return s2st_w2v_conv0_ln_gelu(wave, w, bias, gamma, beta, y, y_bf16, B, N, T, C, k, stride, eps, (hipStream_t)stream);
+}
+int s2st_w2v_ln_gelu_rows_f32(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y_bf16, int32_t rows, int32_t C, float eps, void* stream) {
+  return s2st_w2v_ln_gelu_rows(x, gamma, beta, y, y_bf16, rows, C, eps, (hipStream_t)stream);
+}
+int s2st_w2v_ctc_greedy_i32(const float* logits, const int32_t* lens, int32_t* ids, int32_t* counts, int32_t B, int32_t T, int32_t V, int32_t blank, void* stream) {
+  return s2st_w2v_ctc_greedy(logits, lens, ids, counts, B, T, V, blank, (hipStream_t)stream);
+}
+int s2st_resample_sinc_f32(const float* x, const int32_t* n_in, const float* table, float* y, int32_t B, int32_t N_in, int32_t N_out, int32_t L, int32_t M, int32_t KL, int32_t KW, void* stream) {
+  return s2st_resample_sinc(x, n_in, table, y, B, N_in, N_out, L, M, KL, KW, (hipStream_t)stream);
+}
 #ifndef S2ST_SOURCE_HASH
 #define S2ST_SOURCE_HASH "unknown"  // (__graft_entry__.build passes the hash of the sources; the test emulator build does not)
 #endif

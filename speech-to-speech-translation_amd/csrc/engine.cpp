@@ -364,6 +364,8 @@ struct s2st_engine {
 
 #include "engine_hifigan.h"  // the HiFi-GAN vocoder (--vocoder hifigan)
 
+#include "engine_w2v_ctc.h"  // the wav2vec 2.0 CTC recogniser (ASR-BLEU)
+
 #include "engine_step.h"  // one step
 
 };
@@ -929,6 +931,65 @@ int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames
   e->begin_call(workspace, workspace_floats, stream);
   if (int rc = e->params_ready()) return rc;  // (frozen weights, as in s2st_hubert_forward)
   return e->end_call(e->forward_hifigan(mel, frames, B, T, wave_out));
+}
+
+// ---- wav2vec 2.0 CTC recogniser -------------------------------------------------------------------
+int s2st_w2v_ctc_create(const s2st_w2v_ctc_config* cfg, s2st_engine** out) {
+  if (!cfg || !out || cfg->n_conv < 1 || cfg->n_conv > 8 || cfg->vocab < 1 || cfg->layers < 0 || cfg->heads < 1 ||
+      cfg->conv_pos_groups < 1 || cfg->conv_pos < 1)
+    return S2ST_ERR_ARG;
+  if (cfg->embed % cfg->heads || cfg->embed % cfg->conv_pos_groups || (cfg->embed / cfg->conv_pos_groups) % 4 || cfg->embed % 4 ||
+      cfg->conv_dim[0] > 512 || cfg->conv_k[0] > 16)
+    return S2ST_ERR_SHAPE;
+  for (int i = 0; i < cfg->n_conv; ++i)
+    if (cfg->conv_dim[i] < 4 || cfg->conv_dim[i] % 4 || cfg->conv_dim[i] > 1024 || cfg->conv_k[i] < 1 || cfg->conv_stride[i] < 1)
+      return S2ST_ERR_SHAPE;
+  if (!cfg->precise) {
+    for (int i = 0; i < cfg->n_conv; ++i)
+      if (cfg->conv_dim[i] % 8) return S2ST_ERR_SHAPE;
+    if (cfg->embed % 8 || cfg->ffn % 8 || (cfg->embed / cfg->conv_pos_groups) % 8) return S2ST_ERR_SHAPE;
+  }
+  s2st_engine* e = new s2st_engine();
+  e->is_w2v = true;
+  e->wc = *cfg;
+  e->c = s2st_model_config{};
+  e->c.precise = cfg->precise;
+  e->c.enc_heads = cfg->heads;
+  e->c.enc_dim = cfg->embed;
+  e->ffn_act = 2;
+  // every product goes through the tiled GEMM whatever the batch's row count: an utterance's logits do not depend on what
+  // else is in the batch
+  e->use_skinny = false;
+  e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
+  e->use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
+  e->build_params_w2v_ctc();
+  (void)hipGetLastError();  // (as in s2st_hubert_create)
+  if (!cfg->precise && (s2st_gemm_bf16_preload(nullptr) != 0 || s2st_flash_attn_preload(nullptr) != 0)) { delete e; return S2ST_ERR_LAUNCH; }
+  *out = e;
+  return 0;
+}
+
+int32_t s2st_w2v_ctc_out_frames(const s2st_engine* e, int32_t n_samples) {
+  if (!e || !e->is_w2v) return S2ST_ERR_ARG;
+  return e->w2v_frames(n_samples);
+}
+
+int64_t s2st_w2v_ctc_workspace_floats(s2st_engine* e, int32_t B, int32_t N) {
+  if (!e || !e->is_w2v || B <= 0 || N <= 0) return S2ST_ERR_ARG;
+  // (logits: the dry workspace, never dereferenced; the collapse allocates nothing)
+  return dry_run_floats(e, [&] { return e->forward_w2v_ctc(nullptr, nullptr, nullptr, B, N, 0, e->ws, nullptr, nullptr); });
+}
+
+int s2st_w2v_ctc_forward(s2st_engine* e, const float* wave, const int32_t* sample_lens, const int32_t* frame_lens, int32_t B,
+                         int32_t N, int32_t blank, float* logits_out, int32_t* ids_out, int32_t* counts_out,
+                         float* workspace, int64_t workspace_floats, void* stream) {
+  if (!e || !e->is_w2v || !e->P || !wave || !sample_lens || !frame_lens || !logits_out || (ids_out && !counts_out))
+    return S2ST_ERR_ARG;
+  if (B <= 0 || N <= 0) return S2ST_ERR_SHAPE;
+  if (!workspace) return S2ST_ERR_WORKSPACE;
+  e->begin_call(workspace, workspace_floats, stream);
+  if (int rc = e->params_ready()) return rc;  // (frozen weights, as in s2st_hubert_forward)
+  return e->end_call(e->forward_w2v_ctc(wave, sample_lens, frame_lens, B, N, blank, logits_out, ids_out, counts_out));
 }
 
 }  // extern "C"

@@ -288,6 +288,20 @@ int s2st_posconv_prep(float* x, const int* lens, float* img, uint16_t* imgh, int
                       int Tp, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// wav2vec 2.0 CTC recogniser + resampler (w2v_ctc.hip): waveform normalisation, conv0 + LayerNorm + GELU, LayerNorm + GELU rows,
+// greedy CTC collapse, polyphase windowed-sinc resampling
+// ---------------------------------------------------------------------------------------
+int s2st_w2v_wave_norm(const float* x, const int* lens, float* y, int B, int N, float eps, hipStream_t st);
+int s2st_w2v_conv0_ln_gelu(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, float* y,
+                           uint16_t* yh, int B, int N, int T, int C, int k, int stride, float eps, hipStream_t st);
+int s2st_w2v_ln_gelu_rows(const float* x, const float* gamma, const float* beta, float* y, uint16_t* yh, int rows, int C,
+                          float eps, hipStream_t st);
+int s2st_w2v_ctc_greedy(const float* logits, const int* lens, int* ids, int* counts, int B, int T, int V, int blank,
+                        hipStream_t st);
+int s2st_resample_sinc(const float* x, const int* n_in, const float* table, float* y, int B, int N_in, int N_out, int L, int M,
+                       int KL, int KW, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh
 // ---------------------------------------------------------------------------------------
 // y[b][q up + r][o] = epilogue(bias[o] + sum_{c, j} in[b][q + off[r] + j dil][c] * w[r][o][j][c]) for q < nq; input rows

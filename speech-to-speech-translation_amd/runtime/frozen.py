@@ -1,4 +1,4 @@
-"""Base of the frozen engine-backed networks (the HuBERT front end, the HiFi-GAN vocoder).
+"""Base of the frozen engine-backed networks (the HuBERT front end, the HiFi-GAN vocoder, the wav2vec 2.0 CTC recogniser).
 
 One engine handle made by ``s2st_<kind>_create``, the fp32 parameter arena (and its bf16 copy in fast mode) held by torch,
 a per-geometry workspace plan, and the forward call with the bf16 freshness protocol.  Subclasses add their reference

@@ -1,4 +1,4 @@
-"""Scorers the generation scripts report (``fairseq/scoring``): word error rate.
+"""Scorers the generation scripts report (``fairseq/scoring``): word error rate and sacrebleu's corpus BLEU.
 
 ``WerScorer`` mirrors fairseq/scoring/wer.py:28-61 with its default configuration (tokenizer "none", no lowercasing, no
 punctuation removal, word level): both strings are split on whitespace, the edit distance of the two token lists is
@@ -12,12 +12,22 @@ tokenizer, punctuation removal by Unicode category ``P*``, character tokenisatio
 The reference takes the tokenizers from sacrebleu, which is absent from this image.  ``none`` is the identity.  ``13a``
 (``tokenize_13a``) is a restatement of the published rules of mteval-v13a as sacrebleu states them -- **parity unpinned**:
 no sacrebleu was at hand to compare against.  ``intl``, ``zh`` and ``ja-mecab`` are refused by name.
+
+``SacrebleuScorer`` mirrors fairseq/scoring/bleu.py:46-71: both strings go through ``EvaluationTokenizer``
+(``sacrebleu_tokenizer``, default ``13a``; ``sacrebleu_lowercase``; ``sacrebleu_char_level``) and the score is sacrebleu's
+``corpus_bleu(pred, [ref], tokenize="none")``, restated in ``corpus_bleu`` below from its published definition: clipped
+n-gram counts of orders 1 - 4 summed over the corpus, the default ``exp`` smoothing (the k-th order without a match counts
+as 1 / 2^k of a match; a corpus without any match at all scores 0.0 before smoothing), the brevity penalty ``exp(1 - ref_len / hyp_len)`` for a short system output, the geometric mean of
+the four precisions, and the line sacrebleu's ``.format()`` prints -- **parity unpinned**, for the same reason.  fairseq's
+token-id ``bleu`` scorer (its C extension) stays out of this path.
 """
 from __future__ import annotations
 
 import re
 import unicodedata
-from typing import Sequence
+import math
+from collections import Counter
+from typing import List, Sequence
 
 SPACE, SPACE_ESCAPE = chr(32), chr(9601)
 TOKENIZERS = ("none", "13a")
@@ -108,9 +118,101 @@ class WerScorer:
         return 100.0 * self.distance / self.ref_length if self.ref_length > 0 else 0
 
 
+class BleuScore:
+    """What sacrebleu's ``corpus_bleu`` returns, as far as this path reads it: ``score``, the parts, ``format()``."""
+
+    def __init__(self, score, counts, totals, precisions, bp, sys_len, ref_len):
+        self.score, self.counts, self.totals, self.precisions = score, counts, totals, precisions
+        self.bp, self.sys_len, self.ref_len = bp, sys_len, ref_len
+        self.ratio = sys_len / ref_len if ref_len else 0.0
+
+    def format(self) -> str:
+        prec = "/".join(f"{p:.1f}" for p in self.precisions)
+        return (f"BLEU = {self.score:.2f} {prec} (BP = {self.bp:.3f} ratio = {self.ratio:.3f} hyp_len = {self.sys_len:d} "
+                f"ref_len = {self.ref_len:d})")
+
+    __str__ = format
+
+
+def _ngrams(tokens: Sequence[str], max_order: int) -> Counter:
+    c: Counter = Counter()
+    for n in range(1, max_order + 1):
+        for i in range(len(tokens) - n + 1):
+            c[tuple(tokens[i:i + n])] += 1
+    return c
+
+
+def corpus_bleu(hyps: Sequence[str], refs: Sequence[str], max_order: int = 4) -> BleuScore:
+    """sacrebleu's corpus BLEU of whitespace-tokenised lines against ONE reference each (``tokenize="none"``, smoothing
+    ``exp``, no effective order).  Parity unpinned: restated from the published definition."""
+    if len(hyps) != len(refs):
+        raise ValueError("one reference per hypothesis")
+    counts, totals = [0] * max_order, [0] * max_order
+    sys_len = ref_len = 0
+    for h, r in zip(hyps, refs):
+        ht, rt = h.split(), r.split()
+        sys_len += len(ht)
+        ref_len += len(rt)
+        hn, rn = _ngrams(ht, max_order), _ngrams(rt, max_order)
+        for g, c in hn.items():
+            totals[len(g) - 1] += c
+            counts[len(g) - 1] += min(c, rn.get(g, 0))
+    precisions = [0.0] * max_order
+    if not any(counts):  # no n-gram of any order matches: 0.0 outright, before any smoothing (as sacrebleu does)
+        return BleuScore(0.0, counts, totals, precisions, 0.0, sys_len, ref_len)
+    smooth = 1.0
+    for n in range(max_order):
+        if totals[n] == 0:
+            break
+        if counts[n] == 0:
+            smooth *= 2.0
+            precisions[n] = 100.0 / (smooth * totals[n])
+        else:
+            precisions[n] = 100.0 * counts[n] / totals[n]
+    if sys_len < ref_len:
+        bp = math.exp(1.0 - ref_len / sys_len) if sys_len > 0 else 0.0
+    else:
+        bp = 1.0
+    log = lambda p: math.log(p) if p > 0.0 else -9999999999.0  # noqa: E731  (a precision of zero: a score of zero)
+    score = bp * math.exp(sum(log(p) for p in precisions) / max_order)
+    return BleuScore(score, counts, totals, precisions, bp, sys_len, ref_len)
+
+
+class SacrebleuScorer:
+    def __init__(self, cfg=None):
+        self.cfg = cfg
+        opt = (lambda k, d: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d: getattr(cfg, k, d))
+        self.tokenizer = EvaluationTokenizer(tokenizer_type=opt("sacrebleu_tokenizer", "13a") or "13a",
+                                             lowercase=opt("sacrebleu_lowercase", False),
+                                             character_tokenization=opt("sacrebleu_char_level", False))
+        self.reset()
+
+    def reset(self):
+        self.ref: List[str] = []
+        self.pred: List[str] = []
+
+    def add_string(self, ref: str, pred: str):
+        self.ref.append(self.tokenizer.tokenize(ref))
+        self.pred.append(self.tokenizer.tokenize(pred))
+
+    def corpus(self, order: int = 4) -> BleuScore:
+        if order != 4:
+            raise NotImplementedError
+        return corpus_bleu(self.pred, self.ref)  # (tokenisation and lowercasing were done by self.tokenizer)
+
+    def score(self, order: int = 4) -> float:
+        return self.corpus(order).score
+
+    def result_string(self, order: int = 4) -> str:
+        return self.corpus(order).format()
+
+
 def build_scorer(choice, tgt_dict=None, cfg=None):
-    """fairseq/scoring/__init__.py:39-48 for the scorer this path uses; ``cfg`` carries the ``wer_*`` options."""
+    """fairseq/scoring/__init__.py:39-48 for the scorers this path uses; ``cfg`` carries the ``wer_*`` / ``sacrebleu_*``
+    options."""
     name = getattr(choice, "_name", choice)
+    if name == "sacrebleu":
+        return SacrebleuScorer(cfg)
     if name != "wer":
-        raise ValueError(f"scorer {name!r} is not part of this path (the mtl generator scores with 'wer')")
+        raise ValueError(f"scorer {name!r} is not part of this path (available: 'wer', 'sacrebleu')")
     return WerScorer(cfg)
