@@ -567,6 +567,29 @@ int s2st_gl_overlap_add_b_f32(const float* frames, const float* wsq_all, const i
  * above `tiny`, * n_fft / hop, n_fft / 2 trimmed at both ends); equal to the two calls to fp32 rounding. */
 int s2st_gl_istft_ola_f32(const float* X, const int32_t* tl, const float* win, const float* tw, const float* wsq_all, const int64_t* wsq_off, float* wave, int32_t U, int32_t Tmax, int32_t n_fft, int32_t hop, int32_t Lw, void* stream);
 
+/* Stage 3 data preparation (examples/s2s_trans/preprocessing/get_feature_manifest.py:76-104) for a ragged batch of
+ * utterances: wave [U][Lmax] fp32 with len[u] valid samples -> PACKED feature rows [sum_u T_u][n_bins].  offsets is int32
+ * [2][U + 1], written by the call: frame offsets (utterance u's rows are offsets[u] .. offsets[u + 1]), then pair offsets
+ * (ceil(T_u / 2) each: two frames of ONE utterance share a complex FFT, so a frame's bits do not depend on the batch).
+ * n_pairs = sum_u ceil(T_u / 2) and out_rows = sum_u T_u as the caller computed them from len (grid size, store guard).
+ * tw [n][2] = (cos, -sin)(2 pi j / n); range [n_bins][2] = first bin and one past the last bin of each dense filter row,
+ * summed in index order.
+ * s2st_fbank_kaldi_f32: torchaudio.compliance.kaldi.fbank at its defaults (T_u = 1 + (len - size) / shift, 0 when len < size;
+ * DC removal, pre-emphasis 0.97, window [size], zero padding to `padded` in {256, 512, 1024, 2048}, power spectrum,
+ * banks [n_bins][padded / 2 + 1], log(max(., eps))).
+ * s2st_logmel_f32: extract_logmel_spectrogram (reflect padding n_fft / 2, window [n_fft], magnitude spectrum, mel
+ * [n_mels][n_fft / 2 + 1], log(max(., eps)); T_u = 1 + len / hop, 0 when len <= n_fft / 2) for n_fft that
+ * s2st_gl_fft_supported_i32 accepts.  Other n_fft: s2st_logmel_frame_split_f32 (As [rows][3][n_fft] bf16 = [hi | lo | hi] of
+ * the padded frames, n_fft % 4 == 0) -> s2st_gemm_f32 with the windowed Fourier basis [hi | hi | lo] -> Y [rows][2 Fp] ->
+ * s2st_logmel_from_stft_f32 (F <= 2049).
+ * s2st_feature_moments_f32: moments [U][2][n_bins] = column sums and column sums of squares of each utterance's rows, rows
+ * folded in a fixed order (n_bins <= 256). */
+int s2st_fbank_kaldi_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* banks, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t size, int32_t shift, int32_t padded, int32_t n_bins, float eps, int64_t n_pairs, int64_t out_rows, void* stream);
+int s2st_logmel_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* mel, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int32_t n_mels, float eps, int64_t n_pairs, int64_t out_rows, void* stream);
+int s2st_logmel_frame_split_f32(const float* wave, const int32_t* len, void* As, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int64_t rows, void* stream);
+int s2st_logmel_from_stft_f32(const float* Y, const float* mel, const int32_t* range, float* out, int64_t rows, int32_t F, int32_t Fp, int32_t n_mels, float eps, void* stream);
+int s2st_feature_moments_f32(const float* feats, const int32_t* offsets, float* moments, int32_t U, int32_t n_bins, void* stream);
+
 /* AR decoding (speech_generator_for_s2st.py:76-110: one decoder step for the B utterances of a batch): skinny
  * y[M][N] = f(x[M][K] W[N][K]^T + bias) (+ resid), M <= 16, K % 32 == 0; x fp32 (rounded to bf16 in registers like the
  * operand copies of s2st_gemm_f32), W bf16; act 0 / 1 relu / 2 gelu, dropout mask from (seed, m * N + n) */

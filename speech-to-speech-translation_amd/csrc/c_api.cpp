@@ -310,6 +310,21 @@ int s2st_w2v_ctc_greedy_i32(const float* logits, const int32_t* lens, int32_t* i
 int s2st_resample_sinc_f32(const float* x, const int32_t* n_in, const float* table, float* y, int32_t B, int32_t N_in, int32_t N_out, int32_t L, int32_t M, int32_t KL, int32_t KW, void* stream) {
   return s2st_resample_sinc(x, n_in, table, y, B, N_in, N_out, L, M, KL, KW, (hipStream_t)stream);
 }
+int s2st_fbank_kaldi_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* banks, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t size, int32_t shift, int32_t padded, int32_t n_bins, float eps, int64_t n_pairs, int64_t out_rows, void* stream) {
+  return s2st_fbank_kaldi(wave, len, window, tw, banks, range, out, offsets, U, Lmax, size, shift, padded, n_bins, eps, n_pairs, out_rows, (hipStream_t)stream);
+}
+int s2st_logmel_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* mel, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int32_t n_mels, float eps, int64_t n_pairs, int64_t out_rows, void* stream) {
+  return s2st_logmel(wave, len, window, tw, mel, range, out, offsets, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, (hipStream_t)stream);
+}
+int s2st_logmel_frame_split_f32(const float* wave, const int32_t* len, void* As, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int64_t rows, void* stream) {
+  return s2st_logmel_frame_split(wave, len, (uint16_t*)As, offsets, U, Lmax, n_fft, hop, rows, (hipStream_t)stream);
+}
+int s2st_logmel_from_stft_f32(const float* Y, const float* mel, const int32_t* range, float* out, int64_t rows, int32_t F, int32_t Fp, int32_t n_mels, float eps, void* stream) {
+  return s2st_logmel_from_stft(Y, mel, range, out, rows, F, Fp, n_mels, eps, (hipStream_t)stream);
+}
+int s2st_feature_moments_f32(const float* feats, const int32_t* offsets, float* moments, int32_t U, int32_t n_bins, void* stream) {
+  return s2st_feature_moments(feats, offsets, moments, U, n_bins, (hipStream_t)stream);
+}
 #ifndef S2ST_SOURCE_HASH
 #define S2ST_SOURCE_HASH "unknown"  // (__graft_entry__.build passes the hash of the sources; the test emulator build does not)
 #endif

@@ -302,6 +302,23 @@ int s2st_resample_sinc(const float* x, const int* n_in, const float* table, floa
                        int KL, int KW, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// Stage 3 feature extraction (features.hip): Kaldi filter bank and log-mel spectrogram of a ragged batch wave [U][Lmax] /
+// len [U] into PACKED rows, offs int32 [2][U + 1] = frame offsets, then pair offsets (written by the launchers);
+// per-utterance moments for the global CMVN statistics
+// ---------------------------------------------------------------------------------------
+int s2st_fbank_kaldi(const float* wave, const int* len, const float* win, const float* tw, const float* banks, const int* range,
+                     float* out, int* offs, int U, int Lmax, int size, int shift, int padded, int n_bins, float eps, long n_pairs,
+                     long out_rows, hipStream_t st);
+int s2st_logmel(const float* wave, const int* len, const float* win, const float* tw, const float* mel, const int* range,
+                float* out, int* offs, int U, int Lmax, int n_fft, int hop, int n_mels, float eps, long n_pairs, long out_rows,
+                hipStream_t st);
+int s2st_logmel_frame_split(const float* wave, const int* len, uint16_t* As, int* offs, int U, int Lmax, int n_fft, int hop,
+                            long rows, hipStream_t st);
+int s2st_logmel_from_stft(const float* Y, const float* mel, const int* range, float* out, long rows, int F, int Fp, int n_mels,
+                          float eps, hipStream_t st);
+int s2st_feature_moments(const float* feats, const int* offs, float* mom, int U, int n_bins, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh
 // ---------------------------------------------------------------------------------------
 // y[b][q up + r][o] = epilogue(bias[o] + sum_{c, j} in[b][q + off[r] + j dil][c] * w[r][o][j][c]) for q < nq; input rows
