@@ -120,11 +120,19 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
 
 // One tile of one problem: `id` = the workgroup's index among the `nwg` tiles of the problem, `by` = its batch /
 // split-K coordinate (the launch's blockIdx.y; 0 for grouped launches)
+// Rows of the A image the DMA fills.  The 20 pieces (8 rows, 1 KiB) of a 160-row tile do not split over 8 waves, so its
+// image is padded to 192 rows = 3 pieces per wave: the last 32 rows are re-fetches of the rows below the tile (clamped at
+// M like any row) that no fragment read touches -- every wave keeps the same piece count, hence the same counted vmcnt
+// waits and the same interleaved schedule, for 14 % more fill.
+template <int BM, int NW>
+constexpr int dma_a_rows() { return BM % (8 * NW) == 0 ? BM : (BM / (8 * NW) + 1) * (8 * NW); }
+
 template <int BM, int BN, bool AKM, bool BKM, int NS, int NW, bool IL>
 __device__ __forceinline__ void gemm_bf16_dma_tile(const GemmArgs& g, int id, const int nwg, const int by) {
   constexpr int WGN = NW / 2;  // waves: 2 (M) x WGN (N)
   constexpr int WM = BM / 2, WN = BN / WGN, TM = WM / 16, TN = WN / 16;
-  typedef Dma<AKM, BM, NW> DA;
+  static_assert(AKM || dma_a_rows<BM, NW>() == BM, "a padded A image is K-contiguous");
+  typedef Dma<AKM, dma_a_rows<BM, NW>(), NW> DA;
   typedef Dma<BKM, BN, NW> DB;
   typedef Stage<AKM, BM, true> LA;  // fragment readers (same images)
   typedef Stage<BKM, BN, true> LB;
@@ -391,7 +399,7 @@ const char* staged_tag() {
 
 template <int BM, int BN, int NS, int NW, bool IL = false>
 int launch_dma(const GemmArgs& g, dim3 grid, hipStream_t st) {
-  constexpr int LDS = NS * (BM + BN) * 128;
+  constexpr int LDS = NS * (dma_a_rows<BM, NW>() + BN) * 128;
   auto go = [&](auto kern, const char* tag) {
     static bool configured = false;  // one flag per instantiation (the lambda's operator() template)
     if (!configured) {
@@ -404,8 +412,11 @@ int launch_dma(const GemmArgs& g, dim3 grid, hipStream_t st) {
   };
   if (g.A.kmajor && g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, true, true, NS, NW, IL>, dma_tag<BM, BN, true, true, NS, NW, IL>());
   if (g.A.kmajor && !g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, true, false, NS, NW, IL>, dma_tag<BM, BN, true, false, NS, NW, IL>());
-  if (!g.A.kmajor && g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, false, true, NS, NW, IL>, dma_tag<BM, BN, false, true, NS, NW, IL>());
-  return go(gemm_bf16_dma_kernel<BM, BN, false, false, NS, NW, IL>, dma_tag<BM, BN, false, false, NS, NW, IL>());
+  if constexpr (dma_a_rows<BM, NW>() == BM) {  // (160-row tiles: K-contiguous A only)
+    if (!g.A.kmajor && g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, false, true, NS, NW, IL>, dma_tag<BM, BN, false, true, NS, NW, IL>());
+    return go(gemm_bf16_dma_kernel<BM, BN, false, false, NS, NW, IL>, dma_tag<BM, BN, false, false, NS, NW, IL>());
+  }
+  return -1;
 }
 
 template <int BM, int BN, int NS, int NW, bool IL = false>
@@ -1025,8 +1036,16 @@ int w4_mode() {
 // N = 1536 ... 2048 at K = 512 run 10 - 30 % shorter (4584 x 2048 x 512: 17.5 vs 21.4 us; 2800 x 1536 x 512: 11.1 vs 15.8).
 // Between the two 4-wave shapes the fuller last round wins: 128 x 128 tiles over 2 slots per CU against 128 x 64 tiles
 // over 3 (the pick agreed with the faster of the two on every measured shape).
-// Returns 0 (8-wave kernels), else bn of the 128-row 4-wave form.
-int w4_pick(const GemmArgs& g, bool dma_ok) {
+// Round 8, 160 x 128 tiles (K-contiguous A): the same rounds-of-slots count.  Where the 128-row pick needs a second round
+// and 160-row tiles fit the chip's slots in ONE (N = 2048 with 4096 < M <= 5120: 33 - 40 row tiles x 16 against 512 slots,
+// <= 32 x 16 with 160 rows), one round of 1.25x tiles beats 1.1 - 1.25 rounds: 23.0 -> 17.7 us was the step at M = 4096
+// (profiles/r06_gemm_m_sweep.txt; tools/gemm_m_sweep.py now runs to M = 5120).  With one
+// round either way (M <= 4096; N = 1536) the smaller tile stays, and products of many rounds are not touched.
+// Returns 0 (8-wave kernels), else bn of the 4-wave form; *bm gets its tile rows (128 or 160).
+bool tile160_ok(const GemmArgs& g) { return g.A.kmajor && g.A.sp.per <= 0 && g.batch == 1; }
+
+int w4_pick(const GemmArgs& g, bool dma_ok, int* bm) {
+  *bm = 128;
   const int mode = w4_mode();
   if (mode == 0 || !dma_ok || g.M < 128) return 0;
   const long tm = (g.M + 127) / 128;
@@ -1035,6 +1054,11 @@ int w4_pick(const GemmArgs& g, bool dma_ok) {
   const long s128 = 2L * data_cus(), s64 = 3L * data_cus();
   const double e128 = (double)t128 / (double)(((t128 + s128 - 1) / s128) * s128);
   const double e64 = (double)t64 / (double)(((t64 + s64 - 1) / s64) * s64);
+  if (tile160_ok(g) && g.N > 64) {
+    const long t160 = (long)((g.M + 159) / 160) * ((g.N + 127) / 128);
+    const long s160 = (long)s2st_gemm_bf16_w4_slots160() * data_cus();
+    if (t160 <= s160 && t128 > s128 && t64 > s64) { *bm = 160; return 128; }
+  }
   // Round 5: many rounds of long K-loops are priced by the steady state, not by the last round's fill -- per flop the
   // 128 x 128 tile needs 2/3 of the LDS reads of the 128 x 64 one.  HuBERT's conv stack (307 k / 154 k rows x 512 x 1536):
   // 632 vs 750 us and 342 vs 402 us, where the fill rule took 128 x 64 (25.0 full rounds against 18.75);
@@ -1170,6 +1194,7 @@ int s2st_gemm_bf16_preload(hipStream_t st) {
     launch_layouts<64, 64, false>(g, grid, st);
     rc |= launch_dma<128, 128, 4, 8, true>(g, grid, st);
     rc |= launch_dma<128, 64, 4, 8, true>(g, grid, st);
+    if (g.A.kmajor) rc |= launch_dma<160, 64, 4, 8, true>(g, grid, st);
     rc |= launch_dma<64, 64, 4, 4, true>(g, grid, st);
     GemmGroup grp{};  // no tiles: the kernels fall straight through
     grp.n = 1;
@@ -1193,7 +1218,13 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
   if (g.ep.mask_y && (!g.cvec || g.N % 4 != 0)) return S2ST_ERR_SHAPE;
   const bool linear_epi = !g.ep.act && g.ep.drop_p == 0.f && !g.ep.mask_y;
   struct Cand { int bm, bn; double eff; };
-  static const Cand cands[3] = {{128, 128, 1.0}, {128, 64, 0.8}, {64, 64, 0.55}};  // (tile-preference weights: round 2's sweep)
+  // (tile-preference weights: round 2's sweep.  160 x 64, round 8: the 128 x 64 kernel with five row blocks per wave, so
+  //  its weight -- a candidate only where it runs in ONE round, K-contiguous A, on the LDS-DMA kernels: N = 512 with
+  //  4096 < M <= 5120, where 128 x 64 needs a second round and the pick used to fall to 144 - 160 tiles of 128 x 128)
+  static const Cand cands[4] = {{128, 128, 1.0}, {128, 64, 0.8}, {160, 64, 0.8}, {64, 64, 0.55}};
+  const bool may_split = g.ep.accumulate && linear_epi && g.C.p && !g.C.h && !g.ep.bias && !g.ep.resid && g.K >= 8 * BK;
+  const bool can160 = vec && gemm_dma_enabled() && dma_layout_ok(g) && tile160_ok(g) && persist_mode() <= 1;
+  static const int splitk_target = s2st_env_int("S2ST_SPLITK_TARGET", 128);
   int bm = 64, bn = 64;
   if (vec) {
     double best = 1e300;
@@ -1201,6 +1232,7 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
       long tiles = (long)((g.M + c.bm - 1) / c.bm) * ((g.N + c.bn - 1) / c.bn) * g.batch;
       const long ncu = data_cus();
       long rounds = (tiles + ncu - 1) / ncu;
+      if (c.bm == 160 && !(can160 && rounds == 1 && (!may_split || tiles >= splitk_target))) continue;  // (never a product that would split K)
       // split-K candidates fill the chip anyway: cost by work / efficiency only
       double cost = (double)rounds * c.bm * c.bn / c.eff;
       if (cost < best) { best = cost; bm = c.bm; bn = c.bn; }
@@ -1209,10 +1241,12 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
   if (vec) {  // tuning aid: S2ST_GEMM_TILE=128x128|128x64|64x64 forces the tile
     const char* force = s2st_env_str("S2ST_GEMM_TILE");  // (read per call: the tests switch it)
     if (force && sscanf(force, "%dx%d", &bm, &bn) != 2) { bm = 64; bn = 64; }
+    // 160x128 (4-wave form) / 160x64 (8-wave ring form): where the product cannot take them, the 128-row tile of that width
+    if (force && bm == 160 && !(can160 && (bn == 128 || bn == 64))) bm = 128;
   }
+  const bool can_split_ = may_split && bm != 160;  // a 160-row tile, picked or forced, runs K unsplit
   const bool forced_p4 = vec && bm == 256 && bn == 256;  // S2ST_GEMM_TILE=256x256: the four-phase form where it can run
   if (bm == 256 && !forced_p4 && !(kExperimental && vec && dma_layout_ok(g) && g.batch == 1)) { bm = 128; bn = 128; }  // 256-row tiles: ring kernels of experimental builds only
-  const bool can_split_ = g.ep.accumulate && linear_epi && g.C.p && !g.C.h && !g.ep.bias && !g.ep.resid && g.K >= 8 * BK;
   if (vec && can_split_ && (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch < 256) { bm = 128; bn = 128; }
   // the 4-wave early-release form (w4_pick above): a forced tile is honoured (S2ST_GEMM_W4 >= 1 puts it on that form)
   int w4bn = 0;
@@ -1220,9 +1254,12 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
     static const int use_dma_w4 = gemm_dma_enabled();
     const bool split_like = can_split_ && (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch < 256;
     if (vec && use_dma_w4 && dma_layout_ok(g) && !split_like && persist_mode() != 2) {
-      if (s2st_env_str("S2ST_GEMM_TILE")) w4bn = (w4_mode() >= 1 && bm == 128 && (bn == 128 || bn == 64)) ? bn : 0;
-      else w4bn = w4_pick(g, true);
-      if (w4bn) { bm = 128; bn = w4bn; }
+      int w4bm = 128;
+      if (s2st_env_str("S2ST_GEMM_TILE")) {
+        if (bm == 160 && bn == 128) { w4bn = 128; w4bm = 160; }  // (the 4-wave form is the only 160 x 128 one)
+        else w4bn = (w4_mode() >= 1 && bm == 128 && (bn == 128 || bn == 64)) ? bn : 0;
+      } else w4bn = w4_pick(g, true, &w4bm);
+      if (w4bn) { bm = w4bm; bn = w4bn; }
     }
   }
   // the 256 x 256 four-phase form (p4_pick above); a forced tile is honoured where the form can run at all
@@ -1249,8 +1286,7 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
   g.splitk = 1;
   g.slab = nullptr;
   if (can_split_ && nt < 256) {
-    static const int target = s2st_env_int("S2ST_SPLITK_TARGET", 128);
-    int want = (int)((target + nt - 1) / nt);
+    int want = (int)((splitk_target + nt - 1) / nt);
     int maxs = g.K / (4 * BK);
     g.splitk = want < maxs ? want : maxs;
     if (g.ws) {
@@ -1297,10 +1333,12 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
     else if (kExperimental && bm == 256 && bn == 128) { if constexpr (kExperimental) rc = launch_dma<256, 128, 3, 8>(g, grid, st); else rc = -1; }
     else if (bm == 128 && bn == 128) rc = launch_dma<128, 128, 4, 8, true>(g, grid, st);
     else if (bm == 128) rc = launch_dma<128, 64, 4, 8, true>(g, grid, st);
+    else if (bm == 160) rc = bn == 64 ? launch_dma<160, 64, 4, 8, true>(g, grid, st) : -1;
     else rc = launch_dma<64, 64, 4, 4, true>(g, grid, st);
     if (rc) return rc;
   } else
-  if (!vec) launch_layouts<64, 64, false>(g, grid, st);
+  if (bm == 160) return S2ST_ERR_ARG;  // (can160 implies the LDS-DMA kernels: never reached)
+  else if (!vec) launch_layouts<64, 64, false>(g, grid, st);
   else if (bm == 128 && bn == 128) launch_layouts<128, 128, true>(g, grid, st);
   else if (bm == 128) launch_layouts<128, 64, true>(g, grid, st);
   else launch_layouts<64, 64, true>(g, grid, st);

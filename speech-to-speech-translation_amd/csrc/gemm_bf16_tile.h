@@ -272,6 +272,11 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmArgs& g, f32x4 (&ac
         if (ok) *reinterpret_cast<uint4*>(hbase + ro + n) = make_uint4(ax, ay, bx, by);
       }
     }
+    if constexpr (TM % 2 == 1) {  // (160-row tiles: five row blocks per wave -- the unpaired last one in 8-byte pieces)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        if (mok[TM - 1] && nok[j]) *reinterpret_cast<uint2*>(hbase + roff[TM - 1] + ncol[j]) = hp[TM - 1][j];
+    }
   }
 }
 
@@ -338,6 +343,11 @@ __device__ __forceinline__ void gemm_epilogue_fast_masky(const GemmArgs& g, f32x
       if (ok) *reinterpret_cast<uint4*>(hbase + ro + n) = make_uint4(ax, ay, bx, by);
     }
   }
+  if constexpr (TM % 2 == 1) {  // (the unpaired last row block of a 160-row tile)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+      if (mok[TM - 1] && nok[j]) *reinterpret_cast<uint2*>(hbase + roff[TM - 1] + ncol[j]) = hp[TM - 1][j];
+  }
   if (g.ep.colsum || g.ep.colsum_part) {
     // column sums over the wave's rows (the 16 lanes of a DPP row hold 16 rows of a column group): DPP row sums, then
     // either this (row tile, wave row)'s partial row -- folded in order by the caller, no atomics -- or atomic adds
@@ -364,7 +374,7 @@ template <int BM, int BN, int WGN, bool DROP, bool RESID, bool ACC, bool GELU = 
 __device__ __forceinline__ void gemm_epilogue_fast_out(const GemmArgs& g, f32x4 (&acc)[BM / 32][BN / (16 * WGN)], int m0, int n0,
                                                        int wm, int wn, int lane, int zb, int zq, int zr,
                                                        const float4 (*pre)[BN / (16 * WGN)]) {
-  constexpr bool PAIRS = (BM / 32) % 2 == 0;  // row blocks per wave come in pairs (every tile shape in use)
+  constexpr bool PAIRS = BM / 32 >= 2;  // 16-byte bf16 stores from pairs of row blocks (an odd count leaves one in 8-byte pieces)
   if constexpr (ACC) {
     gemm_epilogue_fast<BM, BN, WGN, DROP, RESID, ACC, true, false, false>(g, acc, m0, n0, wm, wn, lane, zb, zq, zr, pre);
   } else {
@@ -390,10 +400,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[BM
   const bool cvec = g.cvec != 0;
   if constexpr (FAST) {
   if (g.cvec & 8) {  // (launcher: the masked bf16-only form, 16-byte stores)
-    if constexpr ((BM / 32) % 2 == 0) {
-      gemm_epilogue_fast_masky<BM, BN, WGN>(g, acc, m0, n0, wm, wn, lane, zq, zr);
-      return;
-    }
+    gemm_epilogue_fast_masky<BM, BN, WGN>(g, acc, m0, n0, wm, wn, lane, zq, zr);
+    return;
   }
   if (g.cvec & 2) {  // (launcher, mark_fast_epilogue: aligned, N % 4 == 0, no split-K / slab / output mask / column sums / GELU)
     const bool drop = g.ep.drop_p > 0.f, res = g.ep.resid != nullptr, accu = g.ep.accumulate != 0;
@@ -537,6 +545,8 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 //  is re-read by the tiles beside it)
 template <bool KM, int ROWS, int NW>
 struct Dma {
+  static_assert(ROWS % (8 * NW) == 0, "the image's ROWS / 8 pieces of 1 KiB split evenly over the waves");
+  static_assert(KM || (ROWS & (ROWS - 1)) == 0, "rows-contiguous images: a power-of-two number of 16-row groups (kperm)");
   static constexpr int NI = ROWS / (8 * NW);  // wave-instructions per wave per stage (1 KiB each)
   static constexpr int PITCH = KM ? 128 : ROWS * 2;
   static constexpr int BYTES = ROWS * 128;

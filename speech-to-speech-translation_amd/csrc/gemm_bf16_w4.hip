@@ -179,8 +179,11 @@ int launch_w4(const ARG& arg, bool akm, bool bkm, dim3 grid, double fl, double b
   } else {
     if (akm && bkm) return go(gemm_bf16_w4_kernel<BM, BN, true, true, NS>, 3);
     if (akm && !bkm) return go(gemm_bf16_w4_kernel<BM, BN, true, false, NS>, 2);
-    if (!akm && bkm) return go(gemm_bf16_w4_kernel<BM, BN, false, true, NS>, 1);
-    return go(gemm_bf16_w4_kernel<BM, BN, false, false, NS>, 0);
+    if constexpr (BM % 128 == 0) {  // (a 160-row A image exists K-contiguous only)
+      if (!akm && bkm) return go(gemm_bf16_w4_kernel<BM, BN, false, true, NS>, 1);
+      return go(gemm_bf16_w4_kernel<BM, BN, false, false, NS>, 0);
+    }
+    return -1;
   }
 }
 
@@ -196,7 +199,29 @@ int s2st_gemm_bf16_w4(const GemmArgs& g, int bm, int bn, dim3 grid, hipStream_t 
     // 22.0 us with three slots = two workgroups per CU, measured in round 3)
     return launch_w4<128, 64, 2, false>(g, akm, bkm, grid, fl, by, st);
   }
+  if (bm == 160 && bn == 128 && akm) {
+    // K-contiguous A only: wave tile 80 x 64, 2 x 36 KB of ring -- still two workgroups per CU (s2st_gemm_bf16_w4_slots
+    // asks the runtime), so M <= 5120 is 32 row tiles = one round where 128-row tiles need a second one
+    return launch_w4<160, 128, 2, false>(g, akm, bkm, grid, fl, by, st);
+  }
   return S2ST_ERR_ARG;
+}
+
+// workgroups of the 160 x 128 form the runtime places on one CU (w4_pick prices its rounds with it)
+int s2st_gemm_bf16_w4_slots160() {
+  static int slots = -1;
+  if (slots < 0) {
+    int n = w4_wgs_per_cu<160, 128, 2>();
+#ifdef __HIP__  // (the host emulator of the tests has no occupancy query: the LDS arithmetic stands there)
+    constexpr int LDS = 2 * (160 + 128) * 128;
+    auto kern = gemm_bf16_w4_kernel<160, 128, true, true, 2>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, LDS) != hipSuccess)
+      n = 0;
+#endif
+    slots = n;
+  }
+  return slots;
 }
 
 int s2st_gemm_bf16_w4_group(const GemmGroup& grp, hipStream_t st) {
@@ -215,6 +240,7 @@ int s2st_gemm_bf16_w4_preload(hipStream_t st) {
     g.A.kmajor = lay & 1; g.B.kmajor = (lay >> 1) & 1;
     rc |= s2st_gemm_bf16_w4(g, 128, 128, dim3(1), st);
     rc |= launch_w4<128, 64, 2, false>(g, g.A.kmajor != 0, g.B.kmajor != 0, dim3(1), 0.0, 0.0, st);
+    if (g.A.kmajor) rc |= launch_w4<160, 128, 2, false>(g, true, g.B.kmajor != 0, dim3(1), 0.0, 0.0, st);
     GemmGroup grp{};
     grp.n = 1; grp.g[0] = g; grp.total = 0;
     rc |= s2st_gemm_bf16_w4_group(grp, st);

@@ -97,6 +97,7 @@ int s2st_gemm_skinny(const float* A, long lda, const bf16raw* W, long ldw, float
 // gemm_bf16_w4.hip: the 4-wave early-release ring form (2 - 3 workgroups per CU) for the short-K products of a step;
 // g / grp as prepared by s2st_gemm_bf16 / s2st_gemm_bf16_group for the tile (bm, bn)
 int s2st_gemm_bf16_w4(const GemmArgs& g, int bm, int bn, dim3 grid, hipStream_t st);
+int s2st_gemm_bf16_w4_slots160();  // workgroups of the 160 x 128 form per CU, from the runtime's occupancy query
 int s2st_gemm_bf16_w4_group(const GemmGroup& grp, hipStream_t st);
 int s2st_gemm_bf16_w4_preload(hipStream_t st);
 // 256 x 256 four-phase form (gemm_bf16_p4.hip): both operands K-contiguous, chosen by p4_pick() in gemm_bf16.hip

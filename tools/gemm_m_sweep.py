@@ -1,6 +1,8 @@
 """Is there a sawtooth over M (rounds of tiles over the CUs) in the step's data-path products?  For (N, K, epilogue) of the
-four biggest populations: kernel time (events on the dispatch, s2st_profile) for M = 2560 .. 4736 in steps of 64 with the
-launcher's own pick, and the tile it picked.  usage: python tools/gemm_m_sweep.py"""
+biggest populations: kernel time (events on the dispatch, s2st_profile) for M = 2560 .. 5120 in steps of 64 with the
+launcher's own pick, and the tile it picked.  Per point: the median of three measurements (six launches each) and their
+spread.  Epilogues: h = bf16 output, bias + ReLU + dropout (fc1 forward); br = fp32, bias + residual; f = plain fp32 (a
+data gradient); m = masked bf16 output with column sums (fc2's data gradient).  usage: python tools/gemm_m_sweep.py"""
 import importlib, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,7 +14,7 @@ _lib = bd.lib()
 _lib.s2st_profile_enable.argtypes = [C.c_int32]
 _lib.s2st_profile_report.argtypes = [C.c_char_p, C.c_int64]
 _lib.s2st_profile_report.restype = C.c_int64
-MMAX = 4736
+MMAX = 5120
 
 
 def kernel_us(fn, reps=6):
@@ -30,7 +32,8 @@ def kernel_us(fn, reps=6):
     return tot / max(cnt, 1), tags
 
 
-for (N, K, epi) in ((2048, 512, "h"), (512, 2048, "br"), (1536, 512, "h"), (512, 512, "br"), (1024, 512, "h")):
+for (N, K, epi) in ((2048, 512, "h"), (512, 2048, "br"), (1536, 512, "h"), (512, 512, "br"), (1024, 512, "h"), (512, 1536, "f"),
+                    (2048, 512, "m")):
     g = torch.Generator().manual_seed(N + K)
     sets = []
     for _ in range(3):
@@ -40,13 +43,19 @@ for (N, K, epi) in ((2048, 512, "h"), (512, 2048, "br"), (1536, 512, "h"), (512,
         Cf = torch.zeros(MMAX, N, device=d)
         R = torch.randn(MMAX, N, generator=g).to(d)
         bias = torch.randn(N, generator=g).to(d)
-        sets.append((A, B, Ch, Cf, R, bias))
+        Y = torch.relu(torch.randn(MMAX, N, generator=g)).bfloat16().to(d)
+        cs = torch.zeros(N, device=d)
+        sets.append((A, B, Ch, Cf, R, bias, Y, cs))
     print(f"== N {N} K {K} epilogue {epi}")
     for M in range(2560, MMAX + 1, 64):
         def fn(i):
-            A, B, Ch, Cf, R, bias = sets[i % 3]
+            A, B, Ch, Cf, R, bias, Y, cs = sets[i % 3]
             if epi == "h":
                 bd.gemm(A, B, None, M, N, K, a_kmajor=True, b_kmajor=True, a_ld=K, b_ld=K, c_bf16=Ch, bias=bias, act=1, drop_p=0.1, seed=5)
+            elif epi == "f":
+                bd.gemm(A, B, Cf, M, N, K, a_kmajor=True, b_kmajor=True, a_ld=K, b_ld=K)
+            elif epi == "m":
+                bd.gemm(A, B, None, M, N, K, a_kmajor=True, b_kmajor=True, a_ld=K, b_ld=K, c_bf16=Ch, mask_y=Y, mask_scale=1.0 / 0.9, colsum=cs)
             else:
                 bd.gemm(A, B, Cf, M, N, K, a_kmajor=True, b_kmajor=True, a_ld=K, b_ld=K, bias=bias, resid=R)
         fn(0); fn(1)
@@ -56,4 +65,5 @@ for (N, K, epi) in ((2048, 512, "h"), (512, 2048, "br"), (1536, 512, "h"), (512,
             us, tags = kernel_us(fn)
             res.append(us)
         us = statistics.median(res)
-        print(f"M {M:5d}  {us:6.2f} us  {us / M * 128:6.3f} us per 128 rows  {2.0 * M * N * K / us / 1e6:5.0f} TF  {tags[0][:60] if tags else '?'}", flush=True)
+        print(f"M {M:5d}  {us:6.2f} us  spread {max(res) - min(res):5.2f}  {us / M * 128:6.3f} us per 128 rows  {2.0 * M * N * K / us / 1e6:5.0f} TF  "
+              f"{tags[0][:60] if tags else '?'}", flush=True)
