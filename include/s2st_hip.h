@@ -201,6 +201,41 @@ int s2st_bn_apply_f32(const float* x, const float* mean, const float* var, const
 /* backward of bn_apply (train-mode statistics); tmp: S2ST_BN_TMP_FLOATS(C) floats */
 int s2st_bn_bwd_f32(const float* dy, s2st_split dysp, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* dx, s2st_split dxsp, float* dgamma, float* dbeta, float* tmp, int32_t rows, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream);
 
+/* bn_apply written as the next convolution's operand: img = bf16 halo image [B][T + 2 pad][C] (zero halos), y (optional) the
+ * fp32 rows [B * T][C]; C % 4 == 0 */
+int s2st_bn_apply_img_f32(const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* y, uint16_t* img, int32_t B, int32_t T, int32_t pad, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream);
+
+/* bn_stats followed by bn_apply / bn_apply_img in two launches instead of three: the apply kernel folds the statistics'
+ * partial sums itself (same arithmetic, same summation order; mean / var / running statistics are written as by bn_stats) */
+int s2st_bn_stats_apply_f32(const float* x, int32_t rows, int32_t C, float* mean, float* var, float* run_mean, float* run_var, float momentum, float* tmp, const float* gamma, const float* beta, float* y, s2st_split ysp, const float* resid, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream);
+int s2st_bn_stats_apply_img_f32(const float* x, int32_t B, int32_t T, int32_t pad, int32_t C, float* mean, float* var, float* run_mean, float* run_var, float momentum, float* tmp, const float* gamma, const float* beta, float* y, uint16_t* img, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream);
+
+/* bn_bwd that also leaves the plain bf16 twin dxh [rows][ldh] of dx */
+int s2st_bn_bwd_twin_f32(const float* dy, s2st_split dysp, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* dx, s2st_split dxsp, float* dgamma, float* dbeta, float* tmp, int32_t rows, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, uint16_t* dxh, int64_t ldh, void* stream);
+
+/* bn_bwd over rows = B * T in two launches instead of three (the dx kernel folds the sums itself); dxh (optional): the
+ * twin; img (optional): the bf16 halo image [B][T + 2 pad][C] of dx, zero halos (halo_image_bf16 of the twin, stride 1);
+ * C % 4 == 0 */
+int s2st_bn_bwd_fused_f32(const float* dy, s2st_split dysp, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* dx, s2st_split dxsp, float* dgamma, float* dbeta, float* tmp, int32_t B, int32_t T, int32_t pad, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, uint16_t* dxh, int64_t ldh, uint16_t* img, void* stream);
+
+/* y [B][Th][O] bf16 = rows of x [B * Tout][ldx] at u = pad + stride * t, zeros elsewhere (a convolution's data-gradient operand) */
+int s2st_halo_image_bf16_f32(const uint16_t* x, int64_t ldx, uint16_t* y, int32_t B, int32_t Tout, int32_t Th, int32_t O, int32_t pad, int32_t stride, void* stream);
+
+/* bf16 twin [B][T + 2 pad][C] of an fp32 halo image (plain != 0: of the plain rows [B * T][C]); zero halos */
+int s2st_cast_bf16_halo_f32(const float* x, uint16_t* y, int32_t B, int32_t T, int32_t pad, int32_t C, int32_t plain, void* stream);
+
+/* GLU straight into the bf16 halo image [B][T + 2 pad][C]; a: [B * T][2C]; C % 4 == 0 */
+int s2st_glu_fwd_img_f32(const float* a, uint16_t* img, int32_t B, int32_t T, int32_t pad, int32_t C, void* stream);
+
+/* glu_bwd that also leaves the plain bf16 twin dah [rows][ldh] of da */
+int s2st_glu_bwd_twin_f32(const float* a, const float* dy, s2st_split dysp, float* da, s2st_split dasp, int32_t rows, int32_t C, uint16_t* dah, int64_t ldh, void* stream);
+
+/* glu_bwd over rows = B * Tout that also writes img [B][Th][2C] bf16: da's rows at u = pad + stride * t, zeros elsewhere */
+int s2st_glu_bwd_img_f32(const float* a, const float* dy, s2st_split dysp, float* da, s2st_split dasp, int32_t B, int32_t Tout, int32_t Th, int32_t pad, int32_t stride, int32_t C, uint16_t* dah, int64_t ldh, uint16_t* img, void* stream);
+
+/* the gradients of mel_loss with post = feat + postnet(feat): dfeat = feat's own terms + dpost */
+int s2st_mel_loss_resid_f32(const float* feat, const float* post, const float* eos, const float* tgt, const int32_t* lens, int32_t B, int32_t D, int32_t F, float pos_weight, float c_l1, float c_mse, float c_eos, float* dfeat, float* dpost, float* deos, void* stream);
+
 /* s2st_loss.py:294-315 compute_loss: masked L1+MSE (pre/post-net) + BCE(pos_weight) sums and gradients */
 int s2st_mel_loss_f32(const float* feat, const float* post, const float* eos, const float* tgt, const int32_t* lens, int32_t B, int32_t D, int32_t F, float pos_weight, float* stats, float c_l1, float c_mse, float c_eos, float* dfeat, float* dpost, float* deos, void* stream);
 

@@ -313,7 +313,7 @@ __global__ __launch_bounds__(64 * NW, 3) void flash_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int d = 0; d < DT; ++d) {
       const float4 v = make_float4(o[d][0] * inv_l, o[d][1] * inv_l, o[d][2] * inv_l, o[d][3] * inv_l);
-      *reinterpret_cast<float4*>(a.o + ro + 16 * d + 4 * g) = v;
+      if (a.o) *reinterpret_cast<float4*>(a.o + ro + 16 * d + 4 * g) = v;
       if (a.oh) *reinterpret_cast<uint2*>(a.oh + ro + 16 * d + 4 * g) = pack_bf16x4(v.x, v.y, v.z, v.w);
     }
     if (g == 0 && a.lse) a.lse[(long)bh * a.T + qi] = l > 0.f ? m + __logf(l) : -INFINITY;
@@ -957,7 +957,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_short_kernel(AttnArgs a)
 #pragma unroll
     for (int d = 0; d < DT; ++d) {
       const float4 v = make_float4(o[d][0] * inv_l, o[d][1] * inv_l, o[d][2] * inv_l, o[d][3] * inv_l);
-      *reinterpret_cast<float4*>(a.o + ro + 16 * d + 4 * g) = v;
+      if (a.o) *reinterpret_cast<float4*>(a.o + ro + 16 * d + 4 * g) = v;
       if (a.oh) *reinterpret_cast<uint2*>(a.oh + ro + 16 * d + 4 * g) = pack_bf16x4(v.x, v.y, v.z, v.w);
     }
     if (g == 0 && a.lse) a.lse[(long)bh * a.T + qi] = l > 0.f ? m + __logf(l) : -INFINITY;
@@ -1041,7 +1041,8 @@ int s2st_flash_attn_preload(hipStream_t st) {
 }
 
 int s2st_flash_attn_fwd(const s2st_attn_args* p, hipStream_t st) {
-  if (!p || !attn_args_ok(*p) || !p->o || !p->lse) return S2ST_ERR_ARG;
+  // (o == null: only the bf16 copy of O is stored -- every reader of the training step takes that one)
+  if (!p || !attn_args_ok(*p) || (!p->o && !p->oh) || !p->lse) return S2ST_ERR_ARG;
   AttnArgs a = to_args(*p);
   if (p->T <= SHORT_MAX && p->S <= SHORT_MAX && short_fwd_enabled() && short_configure()) {
     const double fl = 4.0 * p->B * p->H * (double)p->T * p->S * p->dh * (p->causal ? 0.5 : 1.0);

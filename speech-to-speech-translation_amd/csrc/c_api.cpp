@@ -129,6 +129,50 @@ int s2st_bn_bwd_f32(const float* dy, s2st_split dysp, const float* x, const floa
   return s2st_bn_bwd(dy, dysp, x, mean, var, gamma, beta, dx, dxsp, dgamma, dbeta, tmp, rows, C, eps, tanh_, drop_p, seed, (hipStream_t)stream);
 }
 
+int s2st_bn_apply_img_f32(const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* y, uint16_t* img, int32_t B, int32_t T, int32_t pad, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream) {
+  return s2st_bn_apply_img(x, mean, var, gamma, beta, y, img, B, T, pad, C, eps, tanh_, drop_p, seed, (hipStream_t)stream);
+}
+
+int s2st_bn_stats_apply_f32(const float* x, int32_t rows, int32_t C, float* mean, float* var, float* run_mean, float* run_var, float momentum, float* tmp, const float* gamma, const float* beta, float* y, s2st_split ysp, const float* resid, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream) {
+  return s2st_bn_stats_apply(x, rows, C, mean, var, run_mean, run_var, momentum, tmp, gamma, beta, y, ysp, resid, eps, tanh_, drop_p, seed, (hipStream_t)stream);
+}
+
+int s2st_bn_stats_apply_img_f32(const float* x, int32_t B, int32_t T, int32_t pad, int32_t C, float* mean, float* var, float* run_mean, float* run_var, float momentum, float* tmp, const float* gamma, const float* beta, float* y, uint16_t* img, float eps, int32_t tanh_, float drop_p, uint64_t seed, void* stream) {
+  return s2st_bn_stats_apply_img(x, B, T, pad, C, mean, var, run_mean, run_var, momentum, tmp, gamma, beta, y, img, eps, tanh_, drop_p, seed, (hipStream_t)stream);
+}
+
+int s2st_bn_bwd_twin_f32(const float* dy, s2st_split dysp, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* dx, s2st_split dxsp, float* dgamma, float* dbeta, float* tmp, int32_t rows, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, uint16_t* dxh, int64_t ldh, void* stream) {
+  return s2st_bn_bwd(dy, dysp, x, mean, var, gamma, beta, dx, dxsp, dgamma, dbeta, tmp, rows, C, eps, tanh_, drop_p, seed, (hipStream_t)stream, dxh, (long)ldh);
+}
+
+int s2st_bn_bwd_fused_f32(const float* dy, s2st_split dysp, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* dx, s2st_split dxsp, float* dgamma, float* dbeta, float* tmp, int32_t B, int32_t T, int32_t pad, int32_t C, float eps, int32_t tanh_, float drop_p, uint64_t seed, uint16_t* dxh, int64_t ldh, uint16_t* img, void* stream) {
+  return s2st_bn_bwd_fused(dy, dysp, x, mean, var, gamma, beta, dx, dxsp, dgamma, dbeta, tmp, B, T, pad, C, eps, tanh_, drop_p, seed, (hipStream_t)stream, dxh, (long)ldh, img);
+}
+
+int s2st_halo_image_bf16_f32(const uint16_t* x, int64_t ldx, uint16_t* y, int32_t B, int32_t Tout, int32_t Th, int32_t O, int32_t pad, int32_t stride, void* stream) {
+  return s2st_halo_image_bf16(x, (long)ldx, y, B, Tout, Th, O, pad, stride, (hipStream_t)stream);
+}
+
+int s2st_cast_bf16_halo_f32(const float* x, uint16_t* y, int32_t B, int32_t T, int32_t pad, int32_t C, int32_t plain, void* stream) {
+  return s2st_cast_bf16_halo(x, y, B, T, pad, C, (hipStream_t)stream, plain);
+}
+
+int s2st_glu_fwd_img_f32(const float* a, uint16_t* img, int32_t B, int32_t T, int32_t pad, int32_t C, void* stream) {
+  return s2st_glu_fwd_img(a, img, B, T, pad, C, (hipStream_t)stream);
+}
+
+int s2st_glu_bwd_twin_f32(const float* a, const float* dy, s2st_split dysp, float* da, s2st_split dasp, int32_t rows, int32_t C, uint16_t* dah, int64_t ldh, void* stream) {
+  return s2st_glu_bwd(a, dy, dysp, da, dasp, rows, C, (hipStream_t)stream, dah, (long)ldh);
+}
+
+int s2st_glu_bwd_img_f32(const float* a, const float* dy, s2st_split dysp, float* da, s2st_split dasp, int32_t B, int32_t Tout, int32_t Th, int32_t pad, int32_t stride, int32_t C, uint16_t* dah, int64_t ldh, uint16_t* img, void* stream) {
+  return s2st_glu_bwd_img(a, dy, dysp, da, dasp, B, Tout, Th, pad, stride, C, (hipStream_t)stream, dah, (long)ldh, img);
+}
+
+int s2st_mel_loss_resid_f32(const float* feat, const float* post, const float* eos, const float* tgt, const int32_t* lens, int32_t B, int32_t D, int32_t F, float pos_weight, float c_l1, float c_mse, float c_eos, float* dfeat, float* dpost, float* deos, void* stream) {
+  return s2st_mel_loss(feat, post, eos, tgt, lens, B, D, F, pos_weight, nullptr, c_l1, c_mse, c_eos, dfeat, dpost, deos, (hipStream_t)stream, nullptr, nullptr, 1);
+}
+
 int s2st_mel_loss_f32(const float* feat, const float* post, const float* eos, const float* tgt, const int32_t* lens, int32_t B, int32_t D, int32_t F, float pos_weight, float* stats, float c_l1, float c_mse, float c_eos, float* dfeat, float* dpost, float* deos, void* stream) {
   return s2st_mel_loss(feat, post, eos, tgt, lens, B, D, F, pos_weight, stats, c_l1, c_mse, c_eos, dfeat, dpost, deos, (hipStream_t)stream);
 }

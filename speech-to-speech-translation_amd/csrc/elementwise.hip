@@ -188,6 +188,69 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ 
   }
 }
 
+// GLU written as the NEXT convolution's operand: the bf16 halo image [B][T + 2 pad][C] of y, zero halos included (what
+// glu_fwd_kernel into an fp32 image + cast_bf16_halo_kernel leave); one thread per 4 channels of an image row.  C % 4 == 0.
+__global__ __launch_bounds__(256) void glu_fwd_img_kernel(const float* __restrict__ a, uint16_t* __restrict__ img, int B, int T,
+                                                          int pad, int C4) {
+  const long i = (long)blockIdx.x * EW_BLOCK + threadIdx.x;
+  const int Th = T + 2 * pad;
+  if (i >= (long)B * Th * C4) return;
+  const int c = (int)(i % C4) * 4;
+  const long bu = i / C4;
+  const int u = (int)(bu % Th), b = (int)(bu / Th);
+  uint2 h = make_uint2(0u, 0u);
+  if (u >= pad && u < pad + T) {
+    const float* ar = a + ((long)b * T + (u - pad)) * (8L * C4);
+    const float4 v = *reinterpret_cast<const float4*>(ar + c), w = *reinterpret_cast<const float4*>(ar + c + 4 * C4);
+    h = pack_bf16x4(v.x * sigmoidf_(w.x), v.y * sigmoidf_(w.y), v.z * sigmoidf_(w.z), v.w * sigmoidf_(w.w));
+  }
+  reinterpret_cast<uint2*>(img)[i] = h;
+}
+
+// glu_bwd_kernel indexed over the bf16 image [B][Th][2C] of da that the producing convolution's data gradient reads: rows
+// at u = pad + stride * t carry da's row (b, t), every other row (halos, the stuffed rows of a stride-2 convolution) is
+// written as zeros; the interior threads also write da (fp32) and its plain bf16 twin.  One thread per 4 channels of
+// each half of an image row.  C % 4 == 0; every plain row is met exactly once (pad + stride * (Tout - 1) < Th).
+__global__ __launch_bounds__(256) void glu_bwd_img_kernel(const float* __restrict__ a, const float* __restrict__ dy, Split dysp,
+                                                          float* __restrict__ da, Split dasp, int B, int Tout, int Th, int pad,
+                                                          int stride, int C4, uint16_t* __restrict__ dah, long ldh,
+                                                          uint16_t* __restrict__ img) {
+  const long i = (long)blockIdx.x * EW_BLOCK + threadIdx.x;
+  if (i >= (long)B * Th * C4) return;
+  const int C = 4 * C4;
+  const int c = (int)(i % C4) * 4;
+  const long bu = i / C4;
+  const int u = (int)(bu % Th), b = (int)(bu / Th);
+  const int d = u - pad;
+  uint2 h0 = make_uint2(0u, 0u), h1 = make_uint2(0u, 0u);
+  if (d >= 0 && d % stride == 0 && d / stride < Tout) {
+    const int r = b * Tout + d / stride;
+    const float* ar = a + (long)r * 2 * C;
+    const float4 av = *reinterpret_cast<const float4*>(ar + c), gv = *reinterpret_cast<const float4*>(ar + c + C);
+    const float4 dv = *reinterpret_cast<const float4*>(dy + split_off(dysp, r) + c);
+    const float as[4] = {av.x, av.y, av.z, av.w}, gt[4] = {gv.x, gv.y, gv.z, gv.w}, gs[4] = {dv.x, dv.y, dv.z, dv.w};
+    float d0[4], d1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float g = gs[k];
+      const float s = sigmoidf_(gt[k]);
+      d0[k] = g * s;
+      d1[k] = g * as[k] * s * (1.f - s);
+    }
+    float* dr = da + split_off(dasp, r);
+    *reinterpret_cast<float4*>(dr + c) = make_float4(d0[0], d0[1], d0[2], d0[3]);
+    *reinterpret_cast<float4*>(dr + c + C) = make_float4(d1[0], d1[1], d1[2], d1[3]);
+    h0 = pack_bf16x4(d0[0], d0[1], d0[2], d0[3]);
+    h1 = pack_bf16x4(d1[0], d1[1], d1[2], d1[3]);
+    if (dah) {
+      *reinterpret_cast<uint2*>(dah + (long)r * ldh + c) = h0;
+      *reinterpret_cast<uint2*>(dah + (long)r * ldh + c + C) = h1;
+    }
+  }
+  *reinterpret_cast<uint2*>(img + bu * (2L * C) + c) = h0;
+  *reinterpret_cast<uint2*>(img + bu * (2L * C) + c + C) = h1;
+}
+
 // spk_table / spk_ids (optional): the utterance's speaker embedding row is added to EVERY position of the utterance,
 // padded ones included, before the dropout (s2st_transformer.py:203-208); T = rows per utterance
 __global__ __launch_bounds__(256) void add_pe_kernel(const float* __restrict__ x,
@@ -587,6 +650,39 @@ struct ShiftSqF {
     return make_float2(d, d * d);
   }
 };
+// Fold of one column's slab partials [slabs][2][cols] in slab order with ALL loads issued together (slabs <= CR_MAX_SLABS:
+// one memory latency; the clamped loads past the last slab re-read it and are not added).  The same sums, bit for bit, as
+// colreduce2_fold_kernel / bn_finalize_shift_kernel form in batches of 16.
+__device__ __forceinline__ float2 fold_slabs_column(const float* __restrict__ part, int slabs, int cols, int c) {
+  float v0[CR_MAX_SLABS], v1[CR_MAX_SLABS];
+#pragma unroll
+  for (int j = 0; j < CR_MAX_SLABS; ++j) {
+    const long s = j < slabs ? j : slabs - 1;
+    v0[j] = part[(s * 2 + 0) * cols + c];
+    v1[j] = part[(s * 2 + 1) * cols + c];
+  }
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+  for (int j = 0; j < CR_MAX_SLABS; ++j)
+    if (j < slabs) { s0 += v0[j]; s1 += v1[j]; }
+  return make_float2(s0, s1);
+}
+// mean / biased variance of one column from its shifted sums {sum d, sum d^2} (d = x - x0), and the running statistics'
+// update (torch: unbiased variance).  One definition for the stand-alone finalize kernel and the fused apply kernels.
+__device__ __forceinline__ float2 bn_finalize_column(float s1, float s2, float x0, int rows, float momentum,
+                                                     float* __restrict__ mean, float* __restrict__ var,
+                                                     float* __restrict__ run_mean, float* __restrict__ run_var) {
+  const float d1 = s1 / rows;
+  const float m = x0 + d1;
+  const float v = fmaxf(s2 / rows - d1 * d1, 0.f);
+  if (mean) { *mean = m; *var = v; }
+  if (run_mean) {
+    *run_mean = (1.f - momentum) * *run_mean + momentum * m;
+    float unb = rows > 1 ? v * ((float)rows / (float)(rows - 1)) : v;
+    *run_var = (1.f - momentum) * *run_var + momentum * unb;
+  }
+  return make_float2(m, v);
+}
 // part: the slab partials [slabs][2][C] of {d, d^2} (folded here, in slab order); x0 = row 0 of x (the shift)
 __global__ __launch_bounds__(256) void bn_finalize_shift_kernel(const float* __restrict__ x0, const float* __restrict__ part,
                                                                 int slabs, float* __restrict__ mean,
@@ -608,16 +704,8 @@ __global__ __launch_bounds__(256) void bn_finalize_shift_kernel(const float* __r
     for (int j = 0; j < 16; ++j)
       if (sb + j < slabs) { s1 += v1[j]; s2 += v2[j]; }
   }
-  const float d1 = s1 / rows;
-  const float m = x0[c] + d1;
-  const float v = fmaxf(s2 / rows - d1 * d1, 0.f);
-  mean[c] = m;
-  var[c] = v;
-  if (run_mean) {
-    run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * m;
-    float unb = rows > 1 ? v * ((float)rows / (float)(rows - 1)) : v;
-    run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-  }
+  bn_finalize_column(s1, s2, x0[c], rows, momentum, mean + c, var + c, run_mean ? run_mean + c : nullptr,
+                     run_mean ? run_var + c : nullptr);
 }
 
 
@@ -670,14 +758,108 @@ __global__ __launch_bounds__(256) void bn_apply_img_kernel(
   reinterpret_cast<uint2*>(img)[i] = h;
 }
 
+// ---- training-mode BatchNorm with the statistics' finalize inside the apply kernel ----------------------------------
+// A workgroup owns BNF_COLS columns and BNF_ROWS rows.  Prologue: one thread per column folds that column's slab partials
+// (what colreduce2_kernel<ShiftSqF> left) and forms mean / var as bn_finalize_shift_kernel does; every workgroup does
+// that for itself from the previous kernel's output (no atomics, no fences), the workgroups of row block 0 also store
+// mean / var and update the running statistics.  One barrier, then the body of bn_apply_kernel / bn_apply_img_kernel.
+constexpr int BNF_COLS = 64, BNF_ROWS = 64;
+struct BnFoldArgs {
+  const float* x0;     // row 0 of x (the shift)
+  const float* part;   // [slabs][2][C]
+  int slabs, rows;
+  float momentum;
+  float *mean, *var, *run_mean, *run_var;
+};
+__device__ __forceinline__ void bn_fold_prologue(const BnFoldArgs& fa, int C, float (*stat)[BNF_COLS]) {
+  const int c = blockIdx.x * BNF_COLS + threadIdx.x;
+  if (threadIdx.x < BNF_COLS && c < C) {
+    const float2 s = fold_slabs_column(fa.part, fa.slabs, C, c);
+    const bool w = blockIdx.y == 0;
+    const float2 mv = bn_finalize_column(s.x, s.y, fa.x0[c], fa.rows, fa.momentum, w ? fa.mean + c : nullptr,
+                                         w ? fa.var + c : nullptr, (w && fa.run_mean) ? fa.run_mean + c : nullptr,
+                                         (w && fa.run_mean) ? fa.run_var + c : nullptr);
+    stat[0][threadIdx.x] = mv.x;
+    stat[1][threadIdx.x] = mv.y;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void bn_apply_fused_kernel(
+    BnFoldArgs fa, const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ y, Split ysp, const float* __restrict__ resid, int rows, int C, float eps, int tanh_, float drop_p,
+    uint64_t seed) {
+  __shared__ float stat[2][BNF_COLS];
+  bn_fold_prologue(fa, C, stat);
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * BNF_COLS + tx;
+  if (c >= C) return;
+  const float mean = stat[0][tx], var = stat[1][tx], ga = gamma[c], be = beta[c];
+  const int r1 = min(rows, (int)(blockIdx.y + 1) * BNF_ROWS);
+  for (int r = blockIdx.y * BNF_ROWS + ty; r < r1; r += 4) {
+    const long i = (long)r * C + c;
+    float u = ga * (x[i] - mean) * rsqrtf(var + eps) + be;
+    if (tanh_ == 1) u = tanhf(u);
+    else if (tanh_ == 2) u = fmaxf(u, 0.f);
+    if (drop_p > 0.f) u *= drop_scale(seed, (uint64_t)i, drop_p, 1.f / (1.f - drop_p));
+    if (resid) u += resid[i];
+    y[split_off(ysp, r) + c] = u;
+  }
+}
+
+// (rows of the grid's y axis are IMAGE rows: B * (T + 2 pad))
+__global__ __launch_bounds__(256) void bn_apply_img_fused_kernel(
+    BnFoldArgs fa, const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ y, uint16_t* __restrict__ img, int B, int T, int pad, int C, float eps, int tanh_, float drop_p,
+    uint64_t seed) {
+  __shared__ float stat[2][BNF_COLS];
+  bn_fold_prologue(fa, C, stat);
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int c = blockIdx.x * BNF_COLS + 4 * tx;
+  if (c >= C) return;  // (C % 4 == 0: a thread's four columns are all inside or all outside)
+  float mean[4], var[4], ga[4], be[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    mean[k] = stat[0][4 * tx + k]; var[k] = stat[1][4 * tx + k];
+    ga[k] = gamma[c + k]; be[k] = beta[c + k];
+  }
+  const int Th = T + 2 * pad;
+  const long nimg = (long)B * Th;
+  const long bu1 = nimg < (long)(blockIdx.y + 1) * BNF_ROWS ? nimg : (long)(blockIdx.y + 1) * BNF_ROWS;
+  for (long bu = (long)blockIdx.y * BNF_ROWS + ty; bu < bu1; bu += 16) {
+    const int u = (int)(bu % Th), b = (int)(bu / Th);
+    uint2 h = make_uint2(0u, 0u);
+    if (u >= pad && u < pad + T) {
+      const long e0 = ((long)b * T + (u - pad)) * C + c;  // element index in the plain [B * T][C] rows
+      const float4 xv = *reinterpret_cast<const float4*>(x + e0);
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+      float o[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float t = ga[k] * (xs[k] - mean[k]) * rsqrtf(var[k] + eps) + be[k];
+        if (tanh_ == 1) t = tanhf(t);
+        else if (tanh_ == 2) t = fmaxf(t, 0.f);
+        if (drop_p > 0.f) t *= drop_scale(seed, (uint64_t)(e0 + k), drop_p, 1.f / (1.f - drop_p));
+        o[k] = t;
+      }
+      if (y) *reinterpret_cast<float4*>(y + e0) = make_float4(o[0], o[1], o[2], o[3]);
+      h = pack_bf16x4(o[0], o[1], o[2], o[3]);
+    }
+    *reinterpret_cast<uint2*>(img + bu * C + c) = h;
+  }
+}
+
 // du = dy * dropmask * (1 - tanh^2)   (recomputed from x);  returns {du, du * xhat}
 struct BnBwdF {
   const float* dy; Split dysp; const float* x; const float* mean; const float* var;
   const float* gamma; const float* beta; int C; float eps; int tanh_; float drop_p; uint64_t seed;
   __device__ float2 operator()(int r, int c) const {
     long i = (long)r * C + c;
-    float xh = (x[i] - mean[c]) * rsqrtf(var[c] + eps);
-    float g = dy[split_off(dysp, r) + c];
+    return at(x[i], dy[split_off(dysp, r) + c], i, c);
+  }
+  // (xv = x[i], g = dy at the same element; i = the element's index in the plain rows)
+  __device__ float2 at(float xv, float g, long i, int c) const {
+    float xh = (xv - mean[c]) * rsqrtf(var[c] + eps);
     if (drop_p > 0.f) g *= drop_scale(seed, (uint64_t)i, drop_p, 1.f / (1.f - drop_p));
     if (tanh_ == 1) {
       float t = tanhf(gamma[c] * xh + beta[c]);
@@ -689,6 +871,18 @@ struct BnBwdF {
   }
 };
 
+// dx of one element: v = {du, du * xhat} of it, xv = x of it, s0 / s1 = the column's sums of du / du * xhat
+__device__ __forceinline__ float bn_bwd_dx_value(const BnBwdF& f, float2 v, float xv, int c, float s0, float s1, int rows) {
+  float rstd = rsqrtf(f.var[c] + f.eps);
+  float xh = (xv - f.mean[c]) * rstd;
+  float inv = 1.f / rows;
+  // v.x - s0 * inv - xh * s1 * inv with its two multiply-adds written out: left to the compiler, the one-element kernel
+  // fuses both while the four-column body of the fused kernel keeps the second product in a packed multiply, and the two
+  // then differ where the three terms cancel (98 ulp seen).  These are the fused forms the one-element kernel always had.
+  const float t = __builtin_fmaf(-s0, inv, v.x);
+  return f.gamma[c] * rstd * __builtin_fmaf(-(xh * s1), inv, t);
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(BnBwdF f, const float* __restrict__ sums,
                                                         float* __restrict__ dx, Split dxsp,
                                                         int rows, int C, uint16_t* __restrict__ dxh, long ldh) {
@@ -697,12 +891,61 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(BnBwdF f, const float* _
   if (i >= n) return;
   int r = (int)(i / C), c = (int)(i - (long)r * C);
   float2 v = f(r, c);  // {du, du*xhat}
-  float rstd = rsqrtf(f.var[c] + f.eps);
-  float xh = (f.x[i] - f.mean[c]) * rstd;
-  float inv = 1.f / rows;
-  const float d = f.gamma[c] * rstd * (v.x - sums[c] * inv - xh * sums[C + c] * inv);
+  const float d = bn_bwd_dx_value(f, v, f.x[i], c, sums[c], sums[C + c], rows);
   dx[split_off(dxsp, r) + c] = d;
   if (dxh) dxh[(long)r * ldh + c] = (uint16_t)(pack_bf16x4(d, 0.f, 0.f, 0.f).x & 0xffffu);  // bf16 twin
+}
+
+// The same with the fold of the slab partials of {sum du, sum du * xhat} in the prologue (as the fused forward kernels:
+// per workgroup, no atomics; row block 0 also adds the sums to dbeta / dgamma), four columns per thread, and -- img != null --
+// the bf16 halo image [B][T + 2 pad][C] of dx (rows at pad + t, zero halos: what halo_image_bf16_kernel makes of the twin
+// for a stride-1 convolution).  The grid's rows are image rows; img == null: pad = 0.
+__global__ __launch_bounds__(256) void bn_bwd_dx_fused_kernel(BnBwdF f, const float* __restrict__ part, int slabs,
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                              float* __restrict__ dx, Split dxsp, int B, int T, int pad,
+                                                              int C, uint16_t* __restrict__ dxh, long ldh,
+                                                              uint16_t* __restrict__ img) {
+  __shared__ float sums[2][BNF_COLS];
+  {
+    const int c = blockIdx.x * BNF_COLS + threadIdx.x;
+    if (threadIdx.x < BNF_COLS && c < C) {
+      const float2 s = fold_slabs_column(part, slabs, C, c);
+      sums[0][threadIdx.x] = s.x;
+      sums[1][threadIdx.x] = s.y;
+      if (blockIdx.y == 0) {
+        if (dbeta) dbeta[c] += s.x;
+        if (dgamma) dgamma[c] += s.y;
+      }
+    }
+    __syncthreads();
+  }
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int c = blockIdx.x * BNF_COLS + 4 * tx;
+  if (c >= C) return;
+  const int rows = B * T, Th = T + 2 * pad;
+  const long nimg = (long)B * Th;
+  const long bu1 = nimg < (long)(blockIdx.y + 1) * BNF_ROWS ? nimg : (long)(blockIdx.y + 1) * BNF_ROWS;
+  for (long bu = (long)blockIdx.y * BNF_ROWS + ty; bu < bu1; bu += 16) {
+    const int u = (int)(bu % Th), b = (int)(bu / Th);
+    uint2 h = make_uint2(0u, 0u);
+    if (u >= pad && u < pad + T) {
+      const int r = b * T + (u - pad);
+      const long e0 = (long)r * C + c;
+      const float4 xv = *reinterpret_cast<const float4*>(f.x + e0);
+      const float4 gv = *reinterpret_cast<const float4*>(f.dy + split_off(f.dysp, r) + c);
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
+      float d[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float2 v = f.at(xs[k], gs[k], e0 + k, c + k);
+        d[k] = bn_bwd_dx_value(f, v, xs[k], c + k, sums[0][4 * tx + k], sums[1][4 * tx + k], rows);
+      }
+      *reinterpret_cast<float4*>(dx + split_off(dxsp, r) + c) = make_float4(d[0], d[1], d[2], d[3]);
+      h = pack_bf16x4(d[0], d[1], d[2], d[3]);
+      if (dxh) *reinterpret_cast<uint2*>(dxh + (long)r * ldh + c) = h;
+    }
+    if (img) *reinterpret_cast<uint2*>(img + bu * C + c) = h;
+  }
 }
 
 __global__ __launch_bounds__(256) void add_vec_kernel(const float* __restrict__ a,
@@ -776,6 +1019,28 @@ int s2st_glu_fwd(const float* a, float* y, Split ysp, int rows, int C, hipStream
   long n = (long)rows * C;
   if (n <= 0) return 0;
   S2ST_LAUNCH(glu_fwd_kernel, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, a, y, ysp, rows, C);
+  return LAUNCH_OK();
+}
+
+int s2st_glu_fwd_img(const float* a, uint16_t* img, int B, int T, int pad, int C, hipStream_t st) {
+  if (B <= 0 || T <= 0 || C <= 0) return 0;
+  if (C % 4 || pad < 0 || ((uintptr_t)a % 16) || ((uintptr_t)img % 8)) return S2ST_ERR_SHAPE;
+  const long n = (long)B * (T + 2 * pad) * (C / 4);
+  S2ST_LAUNCH(glu_fwd_img_kernel, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, a, img, B, T, pad, C / 4);
+  return LAUNCH_OK();
+}
+
+int s2st_glu_bwd_img(const float* a, const float* dy, Split dysp, float* da, Split dasp, int B, int Tout, int Th, int pad,
+                     int stride, int C, hipStream_t st, uint16_t* dah, long ldh, uint16_t* img) {
+  if (B <= 0 || Tout <= 0 || Th <= 0 || C <= 0) return 0;
+  auto sp4 = [](const Split& sp) { return sp.ld % 4 == 0 && sp.bs % 4 == 0; };
+  if (C % 4 || pad < 0 || stride < 1 || pad + (long)stride * (Tout - 1) >= Th || !img || !sp4(dysp) || !sp4(dasp) ||
+      ((uintptr_t)a % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)da % 16) || ((uintptr_t)img % 8) ||
+      (dah && (ldh % 4 || (uintptr_t)dah % 8)))
+    return S2ST_ERR_SHAPE;
+  const long n = (long)B * Th * (C / 4);
+  S2ST_LAUNCH(glu_bwd_img_kernel, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, a, dy, dysp, da, dasp, B, Tout, Th, pad, stride, C / 4,
+              dah, ldh, img);
   return LAUNCH_OK();
 }
 
@@ -1017,6 +1282,39 @@ int s2st_bn_stats(const float* x, int rows, int C, float* mean, float* var, floa
   return LAUNCH_OK();
 }
 
+// s2st_bn_stats + s2st_bn_apply in two launches instead of three: the apply kernel folds the partial sums itself
+int s2st_bn_stats_apply(const float* x, int rows, int C, float* mean, float* var, float* run_mean, float* run_var,
+                        float momentum, float* tmp, const float* gamma, const float* beta, float* y, Split ysp,
+                        const float* resid, float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st) {
+  if (rows <= 0 || C <= 0) return 0;
+  int slabs = 0;
+  float* part = tmp + 2 * (long)C;
+  int rc = colreduce2(ShiftSqF{x, C}, rows, C, nullptr, nullptr, part, st, nullptr, nullptr, &slabs);
+  if (rc) return rc;
+  const BnFoldArgs fa{x, part, slabs, rows, momentum, mean, var, run_mean, run_var};
+  S2ST_LAUNCH(bn_apply_fused_kernel, dim3((C + BNF_COLS - 1) / BNF_COLS, (rows + BNF_ROWS - 1) / BNF_ROWS), dim3(256), 0, st,
+              fa, x, gamma, beta, y, ysp, resid, rows, C, eps, tanh_, drop_p, seed);
+  return LAUNCH_OK();
+}
+
+// s2st_bn_stats + s2st_bn_apply_img likewise (statistics over the B * T plain rows of x)
+int s2st_bn_stats_apply_img(const float* x, int B, int T, int pad, int C, float* mean, float* var, float* run_mean,
+                            float* run_var, float momentum, float* tmp, const float* gamma, const float* beta, float* y,
+                            uint16_t* img, float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st) {
+  if (B <= 0 || T <= 0 || C <= 0) return 0;
+  if (C % 4 || pad < 0 || ((uintptr_t)x % 16) || ((uintptr_t)img % 8) || (y && (uintptr_t)y % 16)) return S2ST_ERR_SHAPE;
+  const int rows = B * T;
+  int slabs = 0;
+  float* part = tmp + 2 * (long)C;
+  int rc = colreduce2(ShiftSqF{x, C}, rows, C, nullptr, nullptr, part, st, nullptr, nullptr, &slabs);
+  if (rc) return rc;
+  const BnFoldArgs fa{x, part, slabs, rows, momentum, mean, var, run_mean, run_var};
+  const long nimg = (long)B * (T + 2 * pad);
+  S2ST_LAUNCH(bn_apply_img_fused_kernel, dim3((C + BNF_COLS - 1) / BNF_COLS, (unsigned)((nimg + BNF_ROWS - 1) / BNF_ROWS)),
+              dim3(256), 0, st, fa, x, gamma, beta, y, img, B, T, pad, C, eps, tanh_, drop_p, seed);
+  return LAUNCH_OK();
+}
+
 int s2st_bn_apply(const float* x, const float* mean, const float* var, const float* gamma,
                   const float* beta, float* y, Split ysp, const float* resid, int rows, int C,
                   float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st) {
@@ -1049,5 +1347,30 @@ int s2st_bn_bwd(const float* dy, Split dysp, const float* x, const float* mean, 
   int rc = colreduce2(f, rows, C, tmp, tmp + C, tmp + 2 * (long)C, st, dbeta, dgamma);
   if (rc) return rc;
   S2ST_LAUNCH(bn_bwd_dx_kernel, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, st, f, tmp, dx, dxsp, rows, C, dxh, ldh);
+  return LAUNCH_OK();
+}
+
+// s2st_bn_bwd in two launches instead of three (the dx kernel folds the partial sums itself), over rows = B * T; img != null:
+// also the bf16 halo image [B][T + 2 pad][C] of dx, as s2st_halo_image_bf16(dxh, ..., stride 1) would make it (img == null: pad
+// is ignored).  tmp as for s2st_bn_bwd.
+int s2st_bn_bwd_fused(const float* dy, Split dysp, const float* x, const float* mean, const float* var, const float* gamma,
+                      const float* beta, float* dx, Split dxsp, float* dgamma, float* dbeta, float* tmp, int B, int T, int pad,
+                      int C, float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st, uint16_t* dxh, long ldh,
+                      uint16_t* img) {
+  if (B <= 0 || T <= 0 || C <= 0) return 0;
+  auto sp4 = [](const Split& sp) { return sp.ld % 4 == 0 && sp.bs % 4 == 0; };
+  if (C % 4 || pad < 0 || !sp4(dysp) || !sp4(dxsp) || ((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)dx % 16) ||
+      (dxh && (ldh % 4 || (uintptr_t)dxh % 8)) || ((uintptr_t)img % 8))
+    return S2ST_ERR_SHAPE;
+  if (!img) pad = 0;
+  const int rows = B * T;
+  BnBwdF f{dy, dysp, x, mean, var, gamma, beta, C, eps, tanh_, drop_p, seed};
+  int slabs = 0;
+  float* part = tmp + 2 * (long)C;
+  int rc = colreduce2(f, rows, C, nullptr, nullptr, part, st, nullptr, nullptr, &slabs);
+  if (rc) return rc;
+  const long nimg = (long)B * (T + 2 * pad);
+  S2ST_LAUNCH(bn_bwd_dx_fused_kernel, dim3((C + BNF_COLS - 1) / BNF_COLS, (unsigned)((nimg + BNF_ROWS - 1) / BNF_ROWS)), dim3(256),
+              0, st, f, (const float*)part, slabs, dgamma, dbeta, dx, dxsp, B, T, pad, C, dxh, ldh, img);
   return LAUNCH_OK();
 }

@@ -44,6 +44,14 @@ struct Ten {  // plain [rows][cols] fp32 activation
   int rows = 0, cols = 0;
   bool needs_grad = true;
   bool want_gh = false;  // the gradient is consumed as a GEMM operand: its producer writes gh too
+  bool gh_only = false;  // ... and ONLY as that operand (fused attention's O): the producer writes no fp32 gradient (g stays allocated, unwritten)
+  // output of conv() whose data gradient reads a bf16 halo image [B][Th][O] (rows at pad + stride * t, zeros elsewhere):
+  // the closure that produces this tensor's gradient (BatchNorm / GLU backward) writes the image itself and leaves it in
+  // gimg; conv()'s closure then skips its own image pass
+  bool img_want = false;
+  int img_B = 0, img_Tout = 0, img_Th = 0, img_pad = 0, img_stride = 1;
+  bf16raw* gimg = nullptr;
+  bool resid_in_loss = false;  // post-net output: the loss root already added this gradient into feat's (post = feat + postnet(feat))
   // produced by linear(act = ReLU, dropout p) with a single consumer (FFN hidden): the consumer's
   // data-gradient GEMM applies the activation backward + bias gradient in its epilogue and leaves the
   // ready bf16 operand in gpre_h (no fp32 gradient of this tensor is ever written)
@@ -280,6 +288,12 @@ struct s2st_engine {
                                // 0.1 to 0.6 ms): it only pays together with wgrad_main_every below
   bool use_act_fuse = true;  // S2ST_NO_ACT_FUSE=1: separate ReLU-dropout backward kernel (A/B switch)
   bool use_flash = true;  // S2ST_NO_FLASH=1: unfused attention everywhere (A/B switch)
+  // S2ST_ATTN_KEEP_F32=1 (A/B switch): the fused attention also stores O in fp32 and the out-projection's data-gradient
+  // GEMM also stores dO in fp32, although every reader takes the bf16 copies
+  bool attn_keep_f32 = s2st_env_on("S2ST_ATTN_KEEP_F32");
+  // S2ST_CONVNET_FUSE=0 (A/B switch): BatchNorm statistics finalize / backward fold / the convolutions' gradient halo
+  // images / the post-net residual add as launches of their own
+  bool convnet_fuse = s2st_env_int("S2ST_CONVNET_FUSE", 1) != 0;
   int ffn_act = 1;        // 1 relu (s2st layers), 2 gelu (HuBERT layers)
   // ---- frozen HuBERT front end (config 4): same engine object in "hubert mode" -------------
   bool is_hubert = false;

@@ -21,6 +21,15 @@
     return s;
   }
 
+  // BatchNorm backward of a convolution's output z in the fused form: the dx kernel folds the sums itself and -- when that
+  // convolution's data gradient reads a bf16 halo image (conv() left the geometry on z) -- writes the image too
+  bool bn_bwd_fusable(const Ten* z, int C) const { return fast() && convnet_fuse && C % 4 == 0 && z->hld() % 4 == 0; }
+  bf16raw* bn_bwd_image(Ten* z, int B, int T) {
+    if (!z->img_want || z->img_stride != 1 || z->img_B != B || z->img_Tout != T || z->img_Th != T + 2 * z->img_pad) return nullptr;
+    z->gimg = alloc_h((long)B * z->img_Th * z->cols);
+    return z->gimg;
+  }
+
   // post-net: 5 x (conv k5 -> BatchNorm -> tanh -> dropout), + residual (tacotron2.py:101-126).
   // Training: batch statistics over ALL B*D rows; eval: running statistics.
   Ten* postnet(Ten* feat, int B, int D, bool tr, std::vector<ConvW>& csp, float* post_out) {
@@ -66,11 +75,19 @@
       }
       if (live()) {
         const float *m = BUF + bn.rm, *v = BUF + bn.rv;
-        if (tr) {
+        // training, fast mode: the statistics' finalize rides in the apply kernel (S2ST_CONVNET_FUSE=0: a launch of its own)
+        const bool fuse = tr && fm && convnet_fuse && bn.C % 4 == 0;
+        if (tr && !fuse) {
           chk(s2st_bn_stats(z->d, B * D, bn.C, mean, var, BUF + bn.rm, BUF + bn.rv, 0.1f, bn_tmp, st_));
           m = mean; v = var;
         }
-        if (nexthh)
+        if (fuse && nexthh)
+          chk(s2st_bn_stats_apply_img(z->d, B, D, pp, bn.C, mean, var, BUF + bn.rm, BUF + bn.rv, 0.1f, bn_tmp, P + bn.g, P + bn.b,
+                                      nullptr, nexthh, 1e-5f, 1, pdrop, sd, st_));
+        else if (fuse)
+          chk(s2st_bn_stats_apply(z->d, B * D, bn.C, mean, var, BUF + bn.rm, BUF + bn.rv, 0.1f, bn_tmp, P + bn.g, P + bn.b, out->d,
+                                  osp, last ? feat->d : nullptr, 1e-5f, last ? 0 : 1, pdrop, sd, st_));
+        else if (nexthh)
           chk(s2st_bn_apply_img(z->d, m, v, P + bn.g, P + bn.b, nullptr, nexthh, B, D, pp, bn.C, 1e-5f, 1, pdrop, sd, st_));
         else
           chk(s2st_bn_apply(z->d, m, v, P + bn.g, P + bn.b, out->d, osp, last ? feat->d : nullptr, B * D,
@@ -79,7 +96,7 @@
       BNP bnp = bn;
       tape.push_back([=]() {
         if (!out->g) return;
-        if (last) {  // post = feat + postnet(feat): the residual branch
+        if (last && !out->resid_in_loss) {  // post = feat + postnet(feat): the residual branch (unless the loss root added it already)
           bool acc;
           float* df = gradbuf(feat, acc);
           if (live()) chk(s2st_dropout(out->g, df, feat->n(), 1.f, 0.f, 0, acc ? 1 : 0, st_));
@@ -89,7 +106,12 @@
         (void)acc;
         Split ps{(long)bnp.C, 0, 0, 0};
         if (fast() && !z->gh) z->gh = alloc_h((long)z->rows * z->hld());  // the conv backward's GEMM operand
-        if (live())
+        if (bn_bwd_fusable(z, bnp.C)) {
+          bf16raw* img = bn_bwd_image(z, B, D);
+          if (live())
+            chk(s2st_bn_bwd_fused(out->g, ps, z->d, mean, var, P + bnp.g, P + bnp.b, dz, ps, G + bnp.g, G + bnp.b, bn_tmp, B, D,
+                                  z->img_pad, bnp.C, 1e-5f, last ? 0 : 1, pdrop, sd, st_, z->gh, z->hld(), img));
+        } else if (live())
           chk(s2st_bn_bwd(out->g, ps, z->d, mean, var, P + bnp.g, P + bnp.b, dz, ps, G + bnp.g, G + bnp.b,
                           bn_tmp, B * D, bnp.C, 1e-5f, last ? 0 : 1, pdrop, sd, st_, z->gh, z->hld()));
       });
@@ -145,11 +167,18 @@
       }
       if (live()) {
         const float *m = BUF + bn.rm, *v = BUF + bn.rv;
-        if (tr) {
+        const bool fuse = tr && fm && convnet_fuse && C % 4 == 0;  // (as in postnet())
+        if (tr && !fuse) {
           chk(s2st_bn_stats(z->d, B * T, C, mean, var, BUF + bn.rm, BUF + bn.rv, 0.1f, bn_tmp, st_));
           m = mean; v = var;
         }
-        if (nexthh)
+        if (fuse && nexthh)
+          chk(s2st_bn_stats_apply_img(z->d, B, T, pp, C, mean, var, BUF + bn.rm, BUF + bn.rv, 0.1f, bn_tmp, P + bn.g, P + bn.b,
+                                      nullptr, nexthh, 1e-5f, 2 /* ReLU */, pdrop, sd, st_));
+        else if (fuse)
+          chk(s2st_bn_stats_apply(z->d, B * T, C, mean, var, BUF + bn.rm, BUF + bn.rv, 0.1f, bn_tmp, P + bn.g, P + bn.b, out->d,
+                                  osp, nullptr, 1e-5f, 2 /* ReLU */, pdrop, sd, st_));
+        else if (nexthh)
           chk(s2st_bn_apply_img(z->d, m, v, P + bn.g, P + bn.b, nullptr, nexthh, B, T, pp, C, 1e-5f, 2 /* ReLU */, pdrop, sd, st_));
         else
           chk(s2st_bn_apply(z->d, m, v, P + bn.g, P + bn.b, out->d, osp, nullptr, B * T, C, 1e-5f, 2 /* ReLU */, pdrop, sd, st_));
@@ -162,7 +191,12 @@
         (void)acc;
         Split ps{(long)bnp.C, 0, 0, 0};
         if (fast() && !z->gh) z->gh = alloc_h((long)z->rows * z->hld());
-        if (live())
+        if (bn_bwd_fusable(z, bnp.C)) {
+          bf16raw* img = bn_bwd_image(z, B, T);
+          if (live())
+            chk(s2st_bn_bwd_fused(out->g, ps, z->d, mean, var, P + bnp.g, P + bnp.b, dz, ps, G + bnp.g, G + bnp.b, bn_tmp, B, T,
+                                  z->img_pad, bnp.C, 1e-5f, 2, pdrop, sd, st_, z->gh, z->hld(), img));
+        } else if (live())
           chk(s2st_bn_bwd(out->g, ps, z->d, mean, var, P + bnp.g, P + bnp.b, dz, ps, G + bnp.g, G + bnp.b, bn_tmp, B * T,
                           bnp.C, 1e-5f, 2, pdrop, sd, st_, z->gh, z->hld()));
       });

@@ -164,6 +164,7 @@
             g.B = fm ? (has_wt(w, N, K) ? gemm_rowmajor(PHT + w, N) : gemm_colmajor(PH + w, K)) : gemm_colmajor(P + w, K);
             g.C = gemm_out(dx + r0 * x->cols, x->cols);
             if (fm && !acc && x->gh) g.C.h = x->gh + r0 * x->cols;  // the consumer (attention backward) reads dO as a GEMM operand
+            if (fm && !acc && x->gh && x->gh_only) g.C.p = nullptr;  // ... and nothing reads the fp32 form (dx stays allocated: the consumer's closure tests it)
             g.ep = gemm_epi_default();
             if (fuse_act) {  // dx is the gradient w.r.t. a ReLU+dropout output: emit its pre-activation gradient
               g.C.p = nullptr;
@@ -288,13 +289,21 @@
     const int C = H * dh;
     const int ld = (S + 7) / 8 * 8;
     const bool fm = fast();
-    Ten* o = newT(B * T, C);
-    o->want_gh = true;
-    if (fm && C % 8 == 0) o->h = alloc_h(o->n());
     // fused path (attention.hip): no [B,H,T,S] tensors in HBM.  The head-averaged attention map of
     // the last decoder layer still needs the probabilities, so that one call stays unfused.
-    if (fm && use_flash && s2st_flash_attn_supported(dh) && !attn_mean_out && o->h && io.ldq % 8 == 0 &&
-        io.ldk % 8 == 0 && io.ldv % 8 == 0) {
+    const bool flash = fm && use_flash && s2st_flash_attn_supported(dh) && !attn_mean_out && C % 8 == 0 && io.ldq % 8 == 0 &&
+                       io.ldk % 8 == 0 && io.ldv % 8 == 0;
+    // The fused path's O and dO are only ever read as bf16: the out-projection's GEMMs take half_of(o), the backward
+    // forms D = rowsum(dO * O) from the bf16 copies -- no fp32 O is allocated or stored, and the out-projection's
+    // data-gradient GEMM stores dO as bf16 only (gh_only).  (The skinny out-projection of AR decoding converts fp32 rows
+    // itself: a handful of rows, fp32 O stays.)
+    const bool skinny_reader = !bt.training && use_skinny && B * T <= S2ST_SKINNY_MAX_ROWS;
+    const bool no_f32 = flash && !attn_keep_f32 && !skinny_reader;
+    Ten* o = newT(B * T, C, nullptr, !no_f32);
+    o->want_gh = true;
+    o->gh_only = no_f32;
+    if (fm && C % 8 == 0) o->h = alloc_h(o->n());
+    if (flash) {
       const uint64_t sd = drop_p > 0.f ? next_seed(S2ST_SITE_ATTN, drop_p, B, H, T, S, ld) : 0;
       float* lse = alloc((long)B * H * T);
       s2st_attn_args fa{};
@@ -306,7 +315,7 @@
       // one chain's share of the batch: utterances [b0, b0 + nbat) of every per-utterance array
       auto chain_args = [=](s2st_attn_args a, int b0, int nbat, uint64_t salt) {
         a.q += (long)b0 * T * a.ldq; a.k += (long)b0 * S * a.ldk; a.v += (long)b0 * S * a.ldv;
-        a.o += (long)b0 * T * C; if (a.oh) a.oh += (long)b0 * T * C;
+        if (a.o) a.o += (long)b0 * T * C; if (a.oh) a.oh += (long)b0 * T * C;
         a.lse += (long)b0 * H * T; if (a.klen) a.klen += b0;
         if (a.doh) a.doh += (long)b0 * T * C;
         if (a.dq) a.dq += (long)b0 * T * a.ldq; if (a.dk) a.dk += (long)b0 * S * a.ldk; if (a.dv) a.dv += (long)b0 * S * a.ldv;
@@ -557,6 +566,10 @@
     const int Tin = in.Tin, Tout = (Tin + 2 * pad - p.Kw) / stride + 1;
     const int Th = Tin + 2 * pad;
     Ten* z = newT(B * Tout, p.O);
+    // the data gradient's operand image (see the closure): its geometry rides on z, so that the BatchNorm / GLU backward
+    // that produces z's gradient can write the image itself
+    z->img_want = convnet_fuse && fm && p.O % 8 == 0 && in.src && in.src->needs_grad;
+    z->img_B = B; z->img_Tout = Tout; z->img_Th = Th; z->img_pad = pad; z->img_stride = stride;
     touch(p.w + (long)p.O * p.I * p.Kw);
     touch(p.b + p.O);
     if (live()) {
@@ -588,8 +601,9 @@
       const bool direct = fm && pp.O % 8 == 0;
       const bool need_img = !no_dgrad;
       float* up = (need_img && !direct) ? alloc((long)B * Th * pp.O, true) : nullptr;
-      bf16raw* upd = (need_img && direct) ? alloc_h((long)B * Th * pp.O) : nullptr;
-      if (need_img && live()) {
+      const bool have_img = need_img && direct && z->gimg;  // the producer of dz wrote the image already
+      bf16raw* upd = have_img ? z->gimg : ((need_img && direct) ? alloc_h((long)B * Th * pp.O) : nullptr);
+      if (need_img && !have_img && live()) {
         Split xs{(long)pp.O, 0, 0, 0};
         Split ys{(long)stride * pp.O, (long)Th * pp.O, Tout, 0};
         if (direct) {
@@ -646,9 +660,11 @@
 
   // GLU of z [rows][2C] into a halo-padded image [B][T + 2 pad][C]; returns the plain-gradient
   // holder for the image (its grad is [rows][C] plain)
-  Ten* glu_to(Ten* z, float* y, Split ysp, int Cc) {
-    Ten* holder = newT(z->rows, Cc, y);  // d points at the (possibly halo) image; only g is used plainly
-    if (live()) chk(s2st_glu_fwd(z->d, y, ysp, z->rows, Cc, st_));
+  // imgh (fast mode, y == null): the result is only ever read as the next convolution's bf16 operand image
+  // [B][T + 2 pad][Cc] -- written directly, zero halos included (no fp32 image, no cast pass)
+  Ten* glu_to(Ten* z, float* y, Split ysp, int Cc, bf16raw* imgh = nullptr, int B = 0, int T = 0, int pad = 0) {
+    Ten* holder = newT(z->rows, Cc, y, y != nullptr);  // d points at the (possibly halo) image; only g is used plainly
+    if (live()) chk(imgh ? s2st_glu_fwd_img(z->d, imgh, B, T, pad, Cc, st_) : s2st_glu_fwd(z->d, y, ysp, z->rows, Cc, st_));
     tape.push_back([=]() {
       if (!holder->g) return;
       bool acc;
@@ -656,7 +672,14 @@
       (void)acc;  // single consumer
       Split ds{(long)Cc, 0, 0, 0}, das{(long)2 * Cc, 0, 0, 0};
       if (fast() && !z->gh) z->gh = alloc_h((long)z->rows * z->hld());  // the conv backward's GEMM operand
-      if (live()) chk(s2st_glu_bwd(z->d, holder->g, ds, dz, das, z->rows, Cc, st_, z->gh, z->hld()));
+      // the producing convolution's data-gradient image (stride 2: zero-stuffed) out of the same kernel
+      const bool img = fast() && convnet_fuse && z->img_want && Cc % 4 == 0 && z->hld() == z->cols &&
+                       z->rows == z->img_B * z->img_Tout;
+      if (img) z->gimg = alloc_h((long)z->img_B * z->img_Th * z->cols);
+      if (live())
+        chk(img ? s2st_glu_bwd_img(z->d, holder->g, ds, dz, das, z->img_B, z->img_Tout, z->img_Th, z->img_pad, z->img_stride, Cc,
+                                   st_, z->gh, z->hld(), z->gimg)
+                : s2st_glu_bwd(z->d, holder->g, ds, dz, das, z->rows, Cc, st_, z->gh, z->hld()));
     });
     return holder;
   }

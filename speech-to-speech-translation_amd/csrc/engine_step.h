@@ -224,9 +224,14 @@
     const bf16raw* xh0h = fm ? cast_halo(bt.src, B, S, pad, c.in_dim, true) : nullptr;
     Ten* z1 = conv(ConvIn{xh0, nullptr, S, xh0h}, sub[0], B, 2, cs0);
     const int C1 = c.conv_channels / 2;
-    float* g1h = alloc((long)B * (T1 + 2 * pad) * C1, !fm);
-    Ten* g1 = glu_to(z1, g1h + (long)pad * C1, Split{(long)C1, (long)(T1 + 2 * pad) * C1, T1, 0}, C1);
-    const bf16raw* g1hh = fm ? cast_halo(g1h, B, T1, pad, C1) : nullptr;
+    // fast mode: the first GLU's result is only read as the second convolution's bf16 operand image: written directly
+    // (S2ST_CONVNET_FUSE=0: fp32 image + cast pass)
+    const bool glu_img = fm && convnet_fuse && C1 % 4 == 0;
+    float* g1h = glu_img ? nullptr : alloc((long)B * (T1 + 2 * pad) * C1, !fm);
+    bf16raw* g1img = glu_img ? alloc_h(((long)B * (T1 + 2 * pad) * C1 + 7) / 8 * 8) : nullptr;
+    Ten* g1 = glu_img ? glu_to(z1, nullptr, Split{(long)C1, 0, 0, 0}, C1, g1img, B, T1, pad)
+                      : glu_to(z1, g1h + (long)pad * C1, Split{(long)C1, (long)(T1 + 2 * pad) * C1, T1, 0}, C1);
+    const bf16raw* g1hh = glu_img ? g1img : (fm ? cast_halo(g1h, B, T1, pad, C1) : nullptr);
     Ten* z2 = conv(ConvIn{g1h, g1, T1, g1hh}, sub[1], B, 2, cs1);
     float* x0d = alloc((long)B * E * C);
     Ten* x0 = glu_to(z2, x0d, Split{(long)C, 0, 0, 0}, C);
@@ -486,10 +491,14 @@
         float* dfeat = gradbuf(feat, a1);
         float* dpost = gradbuf(post, a2);
         float* deos = gradbuf(eos, a3);
+        // post = feat + postnet(feat): the loss kernel adds dpost into dfeat itself, the post-net's last closure then skips
+        // its pass over the two (S2ST_CONVNET_FUSE=0: that pass)
+        const bool resid = convnet_fuse && !a1 && !a2;
+        post->resid_in_loss = resid;
         if (live())
           chk(s2st_mel_loss(feat->d, post->d, eos->d, bt.tgt, bt.tgt_lens, B, D, c.out_dim, c.bce_pos_weight,
                             nullptr, gs * c.w_l1 / nf, gs * c.w_mse / nf, gs * c.w_eos / nr, dfeat, dpost, deos,
-                            st_));
+                            st_, nullptr, nullptr, resid ? 1 : 0));
         if (ctc_logits) {
           bool a;
           float* dl = gradbuf(ctc_logits, a);

@@ -33,7 +33,8 @@ __global__ __launch_bounds__(256) void mel_loss_kernel(
     const float* __restrict__ feat, const float* __restrict__ post, const float* __restrict__ eos,
     const float* __restrict__ tgt, const int* __restrict__ lens, int B, int D, int F,
     float pos_weight, float* __restrict__ stats, float c_l1, float c_mse, float c_eos,
-    float* __restrict__ dfeat, float* __restrict__ dpost, float* __restrict__ deos, float* __restrict__ ordered) {
+    float* __restrict__ dfeat, float* __restrict__ dpost, float* __restrict__ deos, float* __restrict__ ordered,
+    int post_resid) {
   __shared__ float red[3][4];
   const long n = (long)B * D * F;
   float a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -52,8 +53,11 @@ __global__ __launch_bounds__(256) void mel_loss_kernel(
     if (dfeat) {
       float s1 = e1 > 0.f ? 1.f : (e1 < 0.f ? -1.f : 0.f);
       float s2 = e2 > 0.f ? 1.f : (e2 < 0.f ? -1.f : 0.f);
-      dfeat[i] = valid ? c_l1 * s1 + c_mse * 2.f * e1 : 0.f;
-      dpost[i] = valid ? c_l1 * s2 + c_mse * 2.f * e2 : 0.f;
+      const float gf = valid ? c_l1 * s1 + c_mse * 2.f * e1 : 0.f;
+      const float gp = valid ? c_l1 * s2 + c_mse * 2.f * e2 : 0.f;
+      // post_resid: post = feat + postnet(feat) -- post's gradient also flows into feat's, added here instead of by a pass of its own
+      dfeat[i] = post_resid ? gf + gp : gf;
+      dpost[i] = gp;
     }
     if (f == 0) {
       float x = eos[row];
@@ -412,13 +416,13 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* __re
 int s2st_mel_loss(const float* feat, const float* post, const float* eos, const float* tgt,
                   const int* lens, int B, int D, int F, float pos_weight, float* stats, float c_l1,
                   float c_mse, float c_eos, float* dfeat, float* dpost, float* deos,
-                  hipStream_t st, float* ordered, int* nblocks_out) {
+                  hipStream_t st, float* ordered, int* nblocks_out, int post_resid) {
   long n = (long)B * D * F;
   if (n <= 0) return 0;
   long blocks = (n + 256 * 4 - 1) / (256 * 4);
   if (blocks > 2048) blocks = 2048;
   S2ST_LAUNCH(mel_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, st, feat, post, eos, tgt,
-                     lens, B, D, F, pos_weight, stats, c_l1, c_mse, c_eos, dfeat, dpost, deos, ordered);
+                     lens, B, D, F, pos_weight, stats, c_l1, c_mse, c_eos, dfeat, dpost, deos, ordered, post_resid);
   if (nblocks_out) *nblocks_out = (int)blocks;
   return LAUNCH_OK();
 }

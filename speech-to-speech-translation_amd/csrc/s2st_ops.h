@@ -195,6 +195,12 @@ int s2st_copy_rows(const float* x, Split xsp, float* y, Split ysp, int rows, int
 int s2st_glu_fwd(const float* a, float* y, Split ysp, int rows, int C, hipStream_t st);
 int s2st_glu_bwd(const float* a, const float* dy, Split dysp, float* da, Split dasp, int rows,
                  int C, hipStream_t st, uint16_t* dah = nullptr /* optional bf16 twin [rows][ldh] */, long ldh = 0);
+// GLU straight into the bf16 halo image [B][T + 2 pad][C] of y (zero halos written too); a: [B * T][2C], C % 4 == 0
+int s2st_glu_fwd_img(const float* a, uint16_t* img, int B, int T, int pad, int C, hipStream_t st);
+// s2st_glu_bwd over rows = B * Tout that also writes img [B][Th][2C] bf16: da's rows at u = pad + stride * t, zeros elsewhere
+// (= s2st_halo_image_bf16 of the twin); C % 4 == 0
+int s2st_glu_bwd_img(const float* a, const float* dy, Split dysp, float* da, Split dasp, int B, int Tout, int Th, int pad,
+                     int stride, int C, hipStream_t st, uint16_t* dah, long ldh, uint16_t* img);
 // y[r][:] = dropout(scale * x[r][:] + alpha * table[pos[r]][:])   (alpha = *alpha_ptr or 1)
 // spk_table / spk_ids (optional): + spk_table[spk_ids[row / T]] before the dropout (speaker conditioning of the encoder)
 int s2st_add_pe(const float* x, float* y, const int* pos, const float* table, int rows, int C,
@@ -258,6 +264,20 @@ int s2st_bn_apply(const float* x, const float* mean, const float* var, const flo
 int s2st_bn_apply_img(const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float* y,
                       uint16_t* img, int B, int T, int pad, int C, float eps, int tanh_, float drop_p, uint64_t seed,
                       hipStream_t st);
+// s2st_bn_stats followed by s2st_bn_apply / s2st_bn_apply_img with the statistics' finalize inside the apply kernel (one
+// launch less; same arithmetic, same summation order).  tmp: S2ST_BN_TMP_FLOATS(C) floats
+int s2st_bn_stats_apply(const float* x, int rows, int C, float* mean, float* var, float* run_mean, float* run_var,
+                        float momentum, float* tmp, const float* gamma, const float* beta, float* y, Split ysp,
+                        const float* resid, float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st);
+int s2st_bn_stats_apply_img(const float* x, int B, int T, int pad, int C, float* mean, float* var, float* run_mean,
+                            float* run_var, float momentum, float* tmp, const float* gamma, const float* beta, float* y,
+                            uint16_t* img, float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st);
+// s2st_bn_bwd over rows = B * T with the sums' fold inside the dx kernel (one launch less) and, img != null, the bf16 halo
+// image [B][T + 2 pad][C] of dx (= s2st_halo_image_bf16 of the twin, stride 1).  C % 4 == 0
+int s2st_bn_bwd_fused(const float* dy, Split dysp, const float* x, const float* mean, const float* var, const float* gamma,
+                      const float* beta, float* dx, Split dxsp, float* dgamma, float* dbeta, float* tmp, int B, int T, int pad,
+                      int C, float eps, int tanh_, float drop_p, uint64_t seed, hipStream_t st, uint16_t* dxh, long ldh,
+                      uint16_t* img);
 // dx (via dxsp) = BN/tanh/dropout backward; dgamma/dbeta += ; tmp = 2*C floats
 int s2st_bn_bwd(const float* dy, Split dysp, const float* x, const float* mean, const float* var,
                 const float* gamma, const float* beta, float* dx, Split dxsp, float* dgamma,
@@ -412,7 +432,8 @@ int s2st_log_offset(float* x, long n, float eps, hipStream_t st);
 int s2st_mel_loss(const float* feat, const float* post, const float* eos, const float* tgt,
                   const int* lens, int B, int D, int F, float pos_weight, float* stats, float c_l1,
                   float c_mse, float c_eos, float* dfeat, float* dpost, float* deos,
-                  hipStream_t st, float* ordered = nullptr, int* nblocks_out = nullptr);
+                  hipStream_t st, float* ordered = nullptr, int* nblocks_out = nullptr, int post_resid = 0);
+// post_resid: post = feat + postnet(feat), so dfeat = (feat's own terms) + dpost (dpost is written as before)
 // ordered (also s2st_ls_ce): scratch of S2ST_LOSS_ORDERED_FLOATS floats -- the workgroups' sums go there instead of into
 // stats by float atomics ([k][nblocks], nblocks returned); s2st_loss_finalize(parts) adds them in workgroup order: the
 // logged sums repeat bit for bit
