@@ -579,7 +579,12 @@ int s2st_decode_attn_f32(const float* q, int64_t ldq, void* k_cache, void* v_cac
  * running"), klen_next = the key lengths the NEXT step's self-attention masks with (:84-85), n_done[step] = how many are
  * finished.  The host reads n_done a few steps late and drops the steps it ran past the stop: no synchronisation per step. */
 int s2st_decode_stop_update_i32(const float* eos_prob, float thr, int32_t step, int32_t max_iter, int32_t B, int32_t* finished, int32_t* out_lens, int32_t* klen_next, int32_t* n_done, void* stream);
+/* s2st_gl_fft_supported_i32: 1 when n_fft has a POWER-OF-TWO plan (256, 512, 1024, 2048).  s2st_fft_len_supported_i32: 1 when
+ * the LDS FFT kernels take n_fft at all -- those four and the mixed-radix sizes 240, 400 and 1200 (2^4 * 3 * 5^2, the n_fft
+ * stage 3 writes): the sizes s2st_gl_stft_project_f32, s2st_gl_istft_frames_f32, s2st_gl_istft_ola_f32 and s2st_logmel_f32
+ * accept (s2st_fbank_kaldi_f32 pads to a power of two). */
 int s2st_gl_fft_supported_i32(int32_t n_fft);
+int s2st_fft_len_supported_i32(int32_t n_fft);
 int s2st_gl_polar_c_f32(const float* mag, const float* ang, const int32_t* tl, float* X, int32_t U, int32_t F, int32_t Tmax, void* stream);
 /* initial phases (vocoder.py:101-102) from the uniform draws themselves: uniform = the doubles numpy's generator produced, utterance
  * u's [F][T_u] block at uniform + offsets[u]; X = mag * exp(i wrap(2 pi u)).  uniform == NULL: the draws come from the device's
@@ -614,7 +619,7 @@ int s2st_gl_istft_ola_f32(const float* X, const int32_t* tl, const float* win, c
  * banks [n_bins][padded / 2 + 1], log(max(., eps))).
  * s2st_logmel_f32: extract_logmel_spectrogram (reflect padding n_fft / 2, window [n_fft], magnitude spectrum, mel
  * [n_mels][n_fft / 2 + 1], log(max(., eps)); T_u = 1 + len / hop, 0 when len <= n_fft / 2) for n_fft that
- * s2st_gl_fft_supported_i32 accepts.  Other n_fft: s2st_logmel_frame_split_f32 (As [rows][3][n_fft] bf16 = [hi | lo | hi] of
+ * s2st_fft_len_supported_i32 accepts.  Other n_fft: s2st_logmel_frame_split_f32 (As [rows][3][n_fft] bf16 = [hi | lo | hi] of
  * the padded frames, n_fft % 4 == 0) -> s2st_gemm_f32 with the windowed Fourier basis [hi | hi | lo] -> Y [rows][2 Fp] ->
  * s2st_logmel_from_stft_f32 (F <= 2049).
  * s2st_feature_moments_f32: moments [U][2][n_bins] = column sums and column sums of squares of each utterance's rows, rows

@@ -254,6 +254,7 @@ int s2st_decode_stop_update_i32(const float* eos_prob, float thr, int32_t step, 
   return s2st_decode_stop_update(eos_prob, thr, step, max_iter, B, finished, out_lens, klen_next, n_done, (hipStream_t)stream);
 }
 int s2st_gl_fft_supported_i32(int32_t n_fft) { return s2st_gl_fft_supported(n_fft) ? 1 : 0; }
+int s2st_fft_len_supported_i32(int32_t n_fft) { return s2st_fft_len_supported(n_fft) ? 1 : 0; }
 int s2st_gl_polar_c_f32(const float* mag, const float* ang, const int32_t* tl, float* X, int32_t U, int32_t F, int32_t Tmax, void* stream) {
   return s2st_gl_polar_c(mag, ang, tl, X, U, F, Tmax, (hipStream_t)stream);
 }

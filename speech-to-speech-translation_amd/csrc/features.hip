@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__
   __shared__ float sp[2][N / 2 + 1];
   __shared__ float red[8];
   const int tid = threadIdx.x;
-  constexpr int F = N / 2 + 1, PN = N / 256, PF = (F + 255) / 256;
+  constexpr int F = N / 2 + 1, PN = FftLds<N>::PN, PF = (F + 255) / 256;
   for (int j = tid; j < N; j += 256) tw[fpad(j)] = twg[j];
   float wn[PN];
 #pragma unroll
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__
         const int n = tid + 256 * i;
         float v[2] = {0.f, 0.f};
         for (int h = 0; h < 2; ++h) {
-          if (!on[h]) continue;
+          if (!on[h] || (N % 256 != 0 && n >= N)) continue;
           int j = (t0 + h) * hop + n - N / 2;
           if (j < 0) j = -j;
           if (j >= L) j = 2 * (L - 1) - j;
@@ -153,14 +153,15 @@ __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__
       }
     }
 #pragma unroll
-    for (int i = 0; i < PN; ++i) buf[fpad(tid + 256 * i)] = x[i];
+    for (int i = 0; i < PN; ++i)
+      if (N % 256 == 0 || tid + 256 * i < N) buf[fpad(tid + 256 * i)] = x[i];
     __syncthreads();
     fft_lds<N, false>(buf, tw, tid);
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
       const int k = tid + 256 * i;
       if (k >= F) continue;
-      const cplx zk = buf[fpad(k)], zn = buf[fpad((N - k) & (N - 1))];
+      const cplx zk = buf[fpad(k)], zn = buf[fpad(FftLds<N>::neg(k))];
       // Y1 = (Z_k + conj Z_{N-k}) / 2 ; Y2 = (Z_k - conj Z_{N-k}) / (2 i)
       const cplx y[2] = {cplx{0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)}, cplx{0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)}};
       for (int h = 0; h < 2; ++h) {
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__
   }
 }
 
-// ---- dense route (n_fft that fft_lds does not cover): frames split for the bf16x3 STFT GEMM, then |.| + mel + log ----------
+// ---- dense route (n_fft that fft_lds.h has no plan for, or DeviceFeatureExtractor(fft=False)): frames split for the bf16x3 STFT GEMM, then |.| + mel + log ----------
 __device__ __forceinline__ void store_split4(uint16_t* dst, long seg, const float v[4]) {
   uint2 hi, lo;
   split_bf16x4(v[0], v[1], v[2], v[3], hi, lo);
@@ -289,12 +290,10 @@ int s2st_fbank_kaldi(const float* wave, const int* len, const float* win, const 
                      long out_rows, hipStream_t st) {
   if (U <= 0) return 0;
   if (size < 2 || size > padded || shift < 1 || n_bins < 1 || Lmax < 1) return S2ST_ERR_SHAPE;
-  switch (padded) {
-    case 256: return feat_fft_launch<256, true>(wave, len, win, tw, banks, range, out, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, out_rows, st);
-    case 512: return feat_fft_launch<512, true>(wave, len, win, tw, banks, range, out, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, out_rows, st);
-    case 1024: return feat_fft_launch<1024, true>(wave, len, win, tw, banks, range, out, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, out_rows, st);
-    case 2048: return feat_fft_launch<2048, true>(wave, len, win, tw, banks, range, out, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, out_rows, st);
-  }
+#define S2ST_FFT_CASE(N) \
+  case N: return feat_fft_launch<N, true>(wave, len, win, tw, banks, range, out, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, out_rows, st);
+  switch (padded) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) }  // (Kaldi pads its frames to a power of two)
+#undef S2ST_FFT_CASE
   return S2ST_ERR_SHAPE;
 }
 
@@ -303,12 +302,10 @@ int s2st_logmel(const float* wave, const int* len, const float* win, const float
                 hipStream_t st) {
   if (U <= 0) return 0;
   if (hop < 1 || n_mels < 1 || Lmax < 1) return S2ST_ERR_SHAPE;
-  switch (n_fft) {
-    case 256: return feat_fft_launch<256, false>(wave, len, win, tw, mel, range, out, offs, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, st);
-    case 512: return feat_fft_launch<512, false>(wave, len, win, tw, mel, range, out, offs, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, st);
-    case 1024: return feat_fft_launch<1024, false>(wave, len, win, tw, mel, range, out, offs, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, st);
-    case 2048: return feat_fft_launch<2048, false>(wave, len, win, tw, mel, range, out, offs, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, st);
-  }
+#define S2ST_FFT_CASE(N) \
+  case N: return feat_fft_launch<N, false>(wave, len, win, tw, mel, range, out, offs, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, st);
+  switch (n_fft) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) S2ST_FFT_MIXED_SIZES(S2ST_FFT_CASE) }
+#undef S2ST_FFT_CASE
   return S2ST_ERR_SHAPE;
 }
 

@@ -503,8 +503,8 @@ __global__ __launch_bounds__(NT) void decode_attn_fast_kernel(const float* __res
 // So both directions are N-point real FFTs: O(N log N) per frame instead of the 2 N (N + 2) multiply-adds of the dense
 // contraction (x 3 in the bf16x3 GEMM form that rounds 1 - 3 used: 137 ms of the 237 ms one 16-utterance batch took).
 // One workgroup transforms TWO frames at once as the real and imaginary part of one complex N-point FFT (Stockham
-// autosort, radix 4 with a final radix 2 when log2 N is odd, in LDS: 8 N bytes + the twiddle table) and separates /
-// merges the two spectra through the Hermitian symmetry.  N = 256 ... 2048 (powers of two); other n_fft keep the GEMM path.
+// autosort in LDS, fft_lds.h: 8 N bytes + the twiddle table) and separates / merges the two spectra through the Hermitian
+// symmetry.  N = 256 ... 2048 (powers of two) and the mixed-radix sizes 240, 400, 1200; other n_fft keep the GEMM path.
 // ------------------------------------------------------------------------------------------------
 // (cplx, fpad, FftLds<N> and fft_lds<N, INV>: fft_lds.h, shared with features.hip)
 
@@ -514,17 +514,35 @@ __global__ __launch_bounds__(NT) void decode_attn_fast_kernel(const float* __res
 // A workgroup walks several pairs; the NEXT pair's samples and this pair's magnitudes are fetched into registers before
 // the transform starts, so the memory round trips run under the butterflies (first version: load -> transform -> load ->
 // store in sequence, ~18 us per pair and workgroup with four workgroups per CU).
-template <int N>
+// Which two rows share a transform: rows 2 * pair, 2 * pair + 1 of the flattened index (a pair may span two utterances) --
+// or, PER_UTT (gl_istft_frames_kernel at the mixed-radix N), frames (2 p, 2 p + 1) of ONE utterance, pair = u * ceil(Tmax / 2)
+// + p: the pairs the one-launch inverse (gl_istft_ola_kernel, which starts its blocks at even frames for these N) forms too,
+// so that the two inverse forms give the same bits: a packed transform's rounding depends on both halves (1e-7 of the frame scale), and the phase
+// projection of the next iteration amplifies that (measured 2e-6 of the waveform scale after three iterations at 240).
+template <int N, bool PER_UTT = false>
 struct PairInfo {
   int tt[2], uu[2], TT[2];
   bool on[2];
+  // row of half h of a pair in the flattened [U][Tmax] index; has(): the row exists
+  static __device__ __forceinline__ long row(long pair, int h, int Tmax) {
+    if constexpr (!PER_UTT) return 2 * pair + h;
+    else {
+      const int PT = (Tmax + 1) / 2;
+      return (pair / PT) * Tmax + 2 * (pair % PT) + h;
+    }
+  }
+  static __device__ __forceinline__ bool has(long pair, int h, long M, int Tmax) {
+    if constexpr (!PER_UTT) return 2 * pair + h < M;
+    else return 2 * (pair % ((Tmax + 1) / 2)) + h < Tmax;
+  }
   __device__ __forceinline__ void set(long pair, long M, int Tmax, const int* tl, int hop, bool need_len) {
     for (int h = 0; h < 2; ++h) {
-      const long m = 2 * pair + h;
-      uu[h] = m < M ? (int)(m / Tmax) : 0;
-      tt[h] = m < M ? (int)(m - (long)uu[h] * Tmax) : 0;
+      const long m = row(pair, h, Tmax);
+      const bool in = has(pair, h, M, Tmax);
+      uu[h] = in ? (int)(m / Tmax) : 0;
+      tt[h] = in ? (int)(m - (long)uu[h] * Tmax) : 0;
       TT[h] = tl[uu[h]];
-      on[h] = m < M && tt[h] < TT[h] && (!need_len || hop * (TT[h] - 1) > N / 2);
+      on[h] = in && tt[h] < TT[h] && (!need_len || hop * (TT[h] - 1) > N / 2);
     }
   }
 };
@@ -537,12 +555,12 @@ __global__ __launch_bounds__(256) void gl_stft_project_kernel(const float* __res
   __shared__ cplx buf[FftLds<N>::SIZE];
   __shared__ cplx tw[FftLds<N>::SIZE];
   const int tid = threadIdx.x;
-  constexpr int F = N / 2 + 1, PN = N / 256, PF = (F + 255) / 256;
+  constexpr int F = N / 2 + 1, PN = FftLds<N>::PN, PF = (F + 255) / 256;
   for (int j = tid; j < N; j += 256) tw[fpad(j)] = twg[j];
   const long M = (long)U * Tmax;
   float wn[PN];
 #pragma unroll
-  for (int i = 0; i < PN; ++i) wn[i] = win[tid + 256 * i];
+  for (int i = 0; i < PN; ++i) wn[i] = (N % 256 == 0 || tid + 256 * i < N) ? win[tid + 256 * i] : 0.f;
   cplx xr[PN];
   auto fetch = [&](const PairInfo<N>& pi) {
 #pragma unroll
@@ -550,7 +568,7 @@ __global__ __launch_bounds__(256) void gl_stft_project_kernel(const float* __res
       const int n = tid + 256 * i;
       float v[2] = {0.f, 0.f};
       for (int h = 0; h < 2; ++h) {
-        if (!pi.on[h]) continue;
+        if (!pi.on[h] || (N % 256 != 0 && n >= N)) continue;
         const int len = hop * (pi.TT[h] - 1);
         int j = pi.tt[h] * hop + n - N / 2;
         if (j < 0) j = -j;
@@ -570,7 +588,8 @@ __global__ __launch_bounds__(256) void gl_stft_project_kernel(const float* __res
     const long m0 = 2 * pair;
     __syncthreads();  // (the previous pair's readers are done with buf)
 #pragma unroll
-    for (int i = 0; i < PN; ++i) buf[fpad(tid + 256 * i)] = xr[i];
+    for (int i = 0; i < PN; ++i)
+      if (N % 256 == 0 || tid + 256 * i < N) buf[fpad(tid + 256 * i)] = xr[i];
     // this pair's magnitudes and the next pair's samples: in flight during the transform
     float mg[PF][2];
 #pragma unroll
@@ -589,7 +608,7 @@ __global__ __launch_bounds__(256) void gl_stft_project_kernel(const float* __res
     for (int i = 0; i < PF; ++i) {
       const int k = tid + 256 * i;
       if (k >= F) continue;
-      const cplx zk = buf[fpad(k)], zn = buf[fpad((N - k) & (N - 1))];
+      const cplx zk = buf[fpad(k)], zn = buf[fpad(FftLds<N>::neg(k))];
       // Y1 = (Z_k + conj Z_{N-k}) / 2 ; Y2 = (Z_k - conj Z_{N-k}) / (2 i)
       const cplx y[2] = {cplx{0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)}, cplx{0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)}};
       for (int h = 0; h < 2; ++h) {
@@ -612,6 +631,9 @@ __global__ __launch_bounds__(256) void gl_stft_project_kernel(const float* __res
   }
 }
 
+template <int N>
+using FramePairs = PairInfo<N, !FftLds<N>::POW2>;
+
 // inverse: frames[m][n] = window[n] * (hop / N) * irfft(X[m])[n] for the two rows of a pair (rows t >= T_u: zeros);
 // the overlap-add kernel above turns the frames into the waveforms.  The next pair's spectra are fetched ahead likewise.
 template <int N>
@@ -621,15 +643,15 @@ __global__ __launch_bounds__(256) void gl_istft_frames_kernel(const cplx* __rest
   __shared__ cplx buf[FftLds<N>::SIZE];
   __shared__ cplx tw[FftLds<N>::SIZE];
   const int tid = threadIdx.x;
-  constexpr int F = N / 2 + 1, PN = N / 256, PF = (F + 255) / 256;
+  constexpr int F = N / 2 + 1, PN = FftLds<N>::PN, PF = (F + 255) / 256;
   for (int j = tid; j < N; j += 256) tw[fpad(j)] = twg[j];
   const float sc = (float)hop / ((float)N * (float)N);
   const long M = (long)U * Tmax;
   float wn[PN];
 #pragma unroll
-  for (int i = 0; i < PN; ++i) wn[i] = win[tid + 256 * i] * sc;
+  for (int i = 0; i < PN; ++i) wn[i] = (N % 256 == 0 || tid + 256 * i < N) ? win[tid + 256 * i] * sc : 0.f;
   cplx xa[PF], xb[PF];
-  auto fetch = [&](const PairInfo<N>& pi, long m0) {
+  auto fetch = [&](const FramePairs<N>& pi, long m0) {
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
       const int k = tid + 256 * i;
@@ -637,14 +659,14 @@ __global__ __launch_bounds__(256) void gl_istft_frames_kernel(const cplx* __rest
       xb[i] = (k < F && pi.on[1]) ? X[(m0 + 1) * F + k] : cplx{0.f, 0.f};
     }
   };
-  PairInfo<N> cur, nxt;
+  FramePairs<N> cur, nxt;
   long pair = blockIdx.x;
   if (pair < npairs) {
     cur.set(pair, M, Tmax, tl, hop, false);
-    fetch(cur, 2 * pair);
+    fetch(cur, FramePairs<N>::row(pair, 0, Tmax));
   }
   for (; pair < npairs; pair += gridDim.x) {
-    const long m0 = 2 * pair;
+    const long m0 = FramePairs<N>::row(pair, 0, Tmax);  // (the pair's second row is m0 + 1)
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
@@ -658,16 +680,17 @@ __global__ __launch_bounds__(256) void gl_istft_frames_kernel(const cplx* __rest
     const long np_ = pair + gridDim.x;
     if (np_ < npairs) {
       nxt.set(np_, M, Tmax, tl, hop, false);
-      fetch(nxt, 2 * np_);
+      fetch(nxt, FramePairs<N>::row(np_, 0, Tmax));
     }
     __syncthreads();
     fft_lds<N, true>(buf, tw, tid);
 #pragma unroll
     for (int i = 0; i < PN; ++i) {
       const int n = tid + 256 * i;
+      if (N % 256 != 0 && n >= N) continue;
       const cplx z = buf[fpad(n)];
-      if (m0 < M) frames[m0 * N + n] = cur.on[0] ? z.x * wn[i] : 0.f;
-      if (m0 + 1 < M) frames[(m0 + 1) * N + n] = cur.on[1] ? z.y * wn[i] : 0.f;
+      if (FramePairs<N>::has(pair, 0, M, Tmax)) frames[m0 * N + n] = cur.on[0] ? z.x * wn[i] : 0.f;
+      if (FramePairs<N>::has(pair, 1, M, Tmax)) frames[(m0 + 1) * N + n] = cur.on[1] ? z.y * wn[i] : 0.f;
     }
     cur = nxt;
   }
@@ -683,7 +706,8 @@ __global__ __launch_bounds__(256) void gl_istft_frames_kernel(const cplx* __rest
 // CU: 329 us per launch against 136 + 164 for the two-kernel form; the transforms are latency-bound and want 3 - 4
 // workgroups per CU.)  Frames are added in ascending order with a barrier between the two frames of a pair, so every sample
 // sees the additions the stand-alone overlap-add makes, in its order (which two frames share a complex transform differs
-// from the kernel above, so a frame's last bits can: 1e-8 relative, tests/test_inference.py).
+// from the kernel above, so a frame's last bits can: 1e-8 relative, tests/test_inference.py -- at the power-of-two N; at
+// the mixed-radix N both kernels pair frames (2 p, 2 p + 1) of an utterance and give the same bits, see PairInfo).
 template <int N>
 __global__ __launch_bounds__(256) void gl_istft_ola_kernel(const cplx* __restrict__ X, const int* __restrict__ tl,
                                                            const float* __restrict__ win, const cplx* __restrict__ twg,
@@ -695,7 +719,7 @@ __global__ __launch_bounds__(256) void gl_istft_ola_kernel(const cplx* __restric
   cplx* tw = buf + FftLds<N>::SIZE;
   float* acc = reinterpret_cast<float*>(tw + FftLds<N>::SIZE);
   const int tid = threadIdx.x, u = blockIdx.y;
-  constexpr int F = N / 2 + 1, PN = N / 256, PF = (F + 255) / 256;
+  constexpr int F = N / 2 + 1, PN = FftLds<N>::PN, PF = (F + 255) / 256;
   const int T = tl[u];
   const int q0 = blockIdx.x * S, q1 = min(q0 + S, Lw);
   const int len = hop * (T - 1);  // samples of this utterance (vocoder.py:95-97: the n_fft / 2 borders are trimmed)
@@ -711,9 +735,13 @@ __global__ __launch_bounds__(256) void gl_istft_ola_kernel(const cplx* __restric
   const float sc = (float)hop / ((float)N * (float)N);
   float wn[PN];
 #pragma unroll
-  for (int i = 0; i < PN; ++i) wn[i] = win[tid + 256 * i] * sc;
+  for (int i = 0; i < PN; ++i) wn[i] = (N % 256 == 0 || tid + 256 * i < N) ? win[tid + 256 * i] * sc : 0.f;
   const int P0 = q0 + N / 2, P1 = min(q1, len) + N / 2;  // owned positions of the untrimmed signal
   const int t_lo = P0 - N + 1 <= 0 ? 0 : (P0 - N + hop) / hop;
+  // mixed sizes: the pairs of gl_istft_frames_kernel, (2 p, 2 p + 1) of the utterance -- start at an even frame (an odd first
+  // frame's predecessor ends in front of P0: its samples are dropped by the flush) and give a frame its real partner even
+  // when that lies beyond the block (transformed, not added); see PairInfo
+  const int t_beg = FftLds<N>::POW2 ? t_lo : (t_lo & ~1);
   const int t_hi = min(T - 1, (P1 - 1) / hop);
   const cplx* Xu = X + (long)u * Tmax * F;
   const float* wsq = wsq_all + wsq_off[u];
@@ -724,12 +752,15 @@ __global__ __launch_bounds__(256) void gl_istft_ola_kernel(const cplx* __restric
     for (int i = 0; i < PF; ++i) {
       const int k = tid + 256 * i;
       xa[i] = (k < F && t <= t_hi) ? Xu[(long)t * F + k] : cplx{0.f, 0.f};
-      xb[i] = (k < F && t + 1 <= t_hi) ? Xu[(long)(t + 1) * F + k] : cplx{0.f, 0.f};
+      if constexpr (FftLds<N>::POW2)
+        xb[i] = (k < F && t + 1 <= t_hi) ? Xu[(long)(t + 1) * F + k] : cplx{0.f, 0.f};
+      else  // (the real partner, also beyond the block)
+        xb[i] = (k < F && t + 1 < T) ? Xu[(long)(t + 1) * F + k] : cplx{0.f, 0.f};
     }
   };
-  fetch(t_lo);
-  int done = t_lo * hop;  // positions in front of `done` are final and flushed
-  for (int t = t_lo; t <= t_hi; t += 2) {
+  fetch(t_beg);
+  int done = t_beg * hop;  // positions in front of `done` are final and flushed
+  for (int t = t_beg; t <= t_hi; t += 2) {
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
@@ -748,12 +779,14 @@ __global__ __launch_bounds__(256) void gl_istft_ola_kernel(const cplx* __restric
 #pragma clang fp contract(off)  // (product rounded, then added: what the frames-through-HBM form does; no fused multiply-add)
 #pragma unroll
       for (int i = 0; i < PN; ++i) {
+        if (N % 256 != 0 && tid + 256 * i >= N) continue;
         const cplx z = buf[fpad(tid + 256 * i)];
         zx[i] = z.x * wn[i];
         zy[i] = z.y * wn[i];
       }
 #pragma unroll
       for (int i = 0; i < PN; ++i) {
+        if (N % 256 != 0 && tid + 256 * i >= N) continue;
         const int sl = (t * hop + tid + 256 * i) & cm;
         acc[sl] = acc[sl] + zx[i];
       }
@@ -762,6 +795,7 @@ __global__ __launch_bounds__(256) void gl_istft_ola_kernel(const cplx* __restric
     if (t + 1 <= t_hi) {
 #pragma unroll
       for (int i = 0; i < PN; ++i) {
+        if (N % 256 != 0 && tid + 256 * i >= N) continue;
         const int sl = ((t + 1) * hop + tid + 256 * i) & cm;
         acc[sl] = acc[sl] + zy[i];
       }
@@ -1143,8 +1177,12 @@ int s2st_gl_overlap_add_b(const float* frames, const float* wsq_all, const long*
   return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
 }
 
-// ---- FFT-based Griffin-Lim launchers (n_fft a power of two in 256 ... 2048) ------------------------------------------
-bool s2st_gl_fft_supported(int n_fft) { return n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048; }
+// ---- FFT-based Griffin-Lim launchers (the n_fft of fft_lds.h's two lists) ---------------------------------------------
+#define S2ST_FFT_IS(N) || n_fft == N
+// the power-of-two plans (what this query has always meant) / every size fft_lds.h has a plan for
+bool s2st_gl_fft_supported(int n_fft) { return false S2ST_FFT_POW2_SIZES(S2ST_FFT_IS); }
+bool s2st_fft_len_supported(int n_fft) { return false S2ST_FFT_POW2_SIZES(S2ST_FFT_IS) S2ST_FFT_MIXED_SIZES(S2ST_FFT_IS); }
+#undef S2ST_FFT_IS
 
 int s2st_gl_polar_c(const float* mag, const float* ang, const int* tl, float* X, int U, int F, int Tmax, hipStream_t st) {
   const long n = (long)U * Tmax * F;
@@ -1174,7 +1212,8 @@ namespace {
 template <int N>
 int gl_fft_launch(int inverse, const float* wave_or_frames, const int* tl, const float* win, const float* tw, const float* mag,
                   float* X, float* frames, int U, int Tmax, int hop, int Lw, hipStream_t st) {
-  const long npairs = ((long)U * Tmax + 1) / 2;
+  // (FramePairs: the inverse transforms of the mixed sizes pair frames within an utterance)
+  const long npairs = !inverse || FftLds<N>::POW2 ? ((long)U * Tmax + 1) / 2 : (long)U * ((Tmax + 1) / 2);
   if (npairs <= 0) return 0;
   // (4 k workgroups at most: a workgroup keeps its twiddle table over the pairs it walks)
   const unsigned grid = (unsigned)(npairs < 4096 ? npairs : 4096);
@@ -1191,12 +1230,9 @@ int gl_fft_launch(int inverse, const float* wave_or_frames, const int* tl, const
 // wave [U][Lw] -> X [U * Tmax][n_fft / 2 + 1] complex (re, im interleaved), projected onto the magnitudes mag [U * Tmax][F]
 int s2st_gl_stft_project(const float* wave, const int* tl, const float* win, const float* tw, const float* mag, float* X, int U,
                          int Tmax, int n_fft, int hop, int Lw, hipStream_t st) {
-  switch (n_fft) {
-    case 256: return gl_fft_launch<256>(0, wave, tl, win, tw, mag, X, nullptr, U, Tmax, hop, Lw, st);
-    case 512: return gl_fft_launch<512>(0, wave, tl, win, tw, mag, X, nullptr, U, Tmax, hop, Lw, st);
-    case 1024: return gl_fft_launch<1024>(0, wave, tl, win, tw, mag, X, nullptr, U, Tmax, hop, Lw, st);
-    case 2048: return gl_fft_launch<2048>(0, wave, tl, win, tw, mag, X, nullptr, U, Tmax, hop, Lw, st);
-  }
+#define S2ST_FFT_CASE(N) case N: return gl_fft_launch<N>(0, wave, tl, win, tw, mag, X, nullptr, U, Tmax, hop, Lw, st);
+  switch (n_fft) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) S2ST_FFT_MIXED_SIZES(S2ST_FFT_CASE) }
+#undef S2ST_FFT_CASE
   return S2ST_ERR_SHAPE;
 }
 
@@ -1216,7 +1252,9 @@ int gl_istft_ola_launch(const float* X, const int* tl, const float* win, const f
   if (R > Tmax) R = Tmax;
   if (R < 1) R = 1;
   const int S = R * hop;
-  const int C = N + 2 * hop <= 2 * N ? 2 * N : 4 * N;
+  // (a power of two >= N + 2 hop -- for a power-of-two N that is 2 N or 4 N; 2048 floats for 1200 / 300)
+  int C = 256;
+  while (C < N + 2 * hop) C *= 2;
   const int lds = 2 * FftLds<N>::SIZE * (int)sizeof(cplx) + C * (int)sizeof(float);
   static int configured = 0;  // (per instantiation)
   if (lds > configured) {
@@ -1233,22 +1271,17 @@ int gl_istft_ola_launch(const float* X, const int* tl, const float* win, const f
 // X [U * Tmax][F] complex -> wave [U][Lw]: inverse transforms, overlap-add, window-sum-square normalisation, trim (one launch)
 int s2st_gl_istft_ola(const float* X, const int* tl, const float* win, const float* tw, const float* wsq_all, const long* wsq_off,
                       float* wave, int U, int Tmax, int n_fft, int hop, int Lw, hipStream_t st) {
-  switch (n_fft) {
-    case 256: return gl_istft_ola_launch<256>(X, tl, win, tw, wsq_all, wsq_off, wave, U, Tmax, hop, Lw, st);
-    case 512: return gl_istft_ola_launch<512>(X, tl, win, tw, wsq_all, wsq_off, wave, U, Tmax, hop, Lw, st);
-    case 1024: return gl_istft_ola_launch<1024>(X, tl, win, tw, wsq_all, wsq_off, wave, U, Tmax, hop, Lw, st);
-    case 2048: return gl_istft_ola_launch<2048>(X, tl, win, tw, wsq_all, wsq_off, wave, U, Tmax, hop, Lw, st);
-  }
+#define S2ST_FFT_CASE(N) case N: return gl_istft_ola_launch<N>(X, tl, win, tw, wsq_all, wsq_off, wave, U, Tmax, hop, Lw, st);
+  switch (n_fft) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) S2ST_FFT_MIXED_SIZES(S2ST_FFT_CASE) }
+#undef S2ST_FFT_CASE
   return S2ST_ERR_ARG;
 }
 // X [U * Tmax][F] complex -> frames [U * Tmax][n_fft] (windowed synthesis frames; s2st_gl_overlap_add_b finishes)
 int s2st_gl_istft_frames(const float* X, const int* tl, const float* win, const float* tw, float* frames, int U, int Tmax,
                          int n_fft, int hop, hipStream_t st) {
-  switch (n_fft) {
-    case 256: return gl_fft_launch<256>(1, nullptr, tl, win, tw, nullptr, const_cast<float*>(X), frames, U, Tmax, hop, 0, st);
-    case 512: return gl_fft_launch<512>(1, nullptr, tl, win, tw, nullptr, const_cast<float*>(X), frames, U, Tmax, hop, 0, st);
-    case 1024: return gl_fft_launch<1024>(1, nullptr, tl, win, tw, nullptr, const_cast<float*>(X), frames, U, Tmax, hop, 0, st);
-    case 2048: return gl_fft_launch<2048>(1, nullptr, tl, win, tw, nullptr, const_cast<float*>(X), frames, U, Tmax, hop, 0, st);
-  }
+#define S2ST_FFT_CASE(N) \
+  case N: return gl_fft_launch<N>(1, nullptr, tl, win, tw, nullptr, const_cast<float*>(X), frames, U, Tmax, hop, 0, st);
+  switch (n_fft) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) S2ST_FFT_MIXED_SIZES(S2ST_FFT_CASE) }
+#undef S2ST_FFT_CASE
   return S2ST_ERR_SHAPE;
 }

@@ -396,9 +396,11 @@ int s2st_gl_frame_split(const float* wave, const int* tl, uint16_t* As, int U, i
                         hipStream_t st);
 int s2st_gl_overlap_add_b(const float* frames, const float* wsq_all, const long* wsq_off, const int* tl, float* wave,
                           int U, int Tmax, int n_fft, int hop, int Lw, hipStream_t st);
-// FFT-based Griffin-Lim (infer.hip): n_fft a power of two in 256 ... 2048; X is complex [U * Tmax][n_fft / 2 + 1] (re, im
+// FFT-based Griffin-Lim (infer.hip): n_fft a power of two in 256 ... 2048 (s2st_gl_fft_supported) or one of the mixed-radix
+// sizes 240 / 400 / 1200 (s2st_fft_len_supported: both lists, fft_lds.h); X is complex [U * Tmax][n_fft / 2 + 1] (re, im
 // interleaved); win [n_fft]; tw [n_fft] complex = exp(-2 pi i j / n_fft)
 bool s2st_gl_fft_supported(int n_fft);
+bool s2st_fft_len_supported(int n_fft);
 int s2st_gl_polar_c(const float* mag, const float* ang, const int* tl, float* X, int U, int F, int Tmax, hipStream_t st);
 // initial phases from uniform draws (uni: utterance u's [F][T_u] block at uni + uoff[u], doubles as numpy drew them) or, uni ==
 // nullptr, from the device's counter-based generator

@@ -103,13 +103,17 @@ def global_cmvn(moments: np.ndarray, n_frames: int) -> Tuple[np.ndarray, np.ndar
 class DeviceFeatureExtractor:
     """``fbank`` / ``logmel`` of lists of 1-D waveforms on ``device``.  Utterances are taken in order into batches of at most
     ``max_samples`` padded samples (U x longest); a batch is one upload, the kernels, and ONE copy back (features and moments
-    in one buffer).  A frame's bits do not depend on the batch it was extracted in."""
+    in one buffer).  A frame's bits do not depend on the batch it was extracted in.
 
-    def __init__(self, device=None, max_samples: int = 1 << 24):
+    ``fft``: the log-mel spectrogram goes through the LDS FFT kernel where the library has a plan for n_fft (256 ... 2048 and
+    240 / 400 / 1200, the stage's default); ``False`` forces the dense bf16x3 product that every other n_fft takes (A/B runs)."""
+
+    def __init__(self, device=None, max_samples: int = 1 << 24, fft: bool = True):
         if device is None:
             device = torch.device("cpu") if bd.is_emulator() else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
         self.max_samples = int(max_samples)
+        self.fft = bool(fft)
         self._tabs = {}
 
     # ---- tables -------------------------------------------------------------------------------------------------------
@@ -133,7 +137,7 @@ class DeviceFeatureExtractor:
         t = self._tabs.get(key)
         if t is None:
             win, mel = logmel_tables(sample_rate, n_fft, win_length, n_mels, f_min, f_max)
-            use_fft = bool(bd.lib().s2st_gl_fft_supported_i32(int(n_fft)))
+            use_fft = self.fft and bool(bd.lib().s2st_fft_len_supported_i32(int(n_fft)))
             t = {"mel": self._dev(mel), "range": self._dev(_ranges(mel)), "fft": use_fft}
             if use_fft:
                 t["win"], t["tw"] = self._dev(win), self._dev(_twiddles(n_fft))

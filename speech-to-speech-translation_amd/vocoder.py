@@ -3,7 +3,8 @@
 GriffinLimVocoder) with the same constructor arguments.
 
 The reference's STFT / inverse STFT are dense-DFT contractions (conv1d / conv_transpose1d with Fourier bases,
-audio_utils.py:259-271, vocoder.py:56-98).  Round 4: for power-of-two n_fft (256 ... 2048) they run as real FFTs in LDS
+audio_utils.py:259-271, vocoder.py:56-98).  Round 4: for power-of-two n_fft (256 ... 2048), and since the
+mixed-radix plans of csrc/fft_lds.h for 240, 400 and 1200 (stage 3's default) too, they run as real FFTs in LDS
 (csrc/infer.hip: the analysis basis is rfft(window * frame), the pseudo-inverse synthesis basis is window * hop / n_fft *
 irfft -- exactly); other n_fft (and S2ST_GL_FFT=0) keep the dense form of rounds 1 - 3: GEMMs on the matrix cores (bf16x3
 "precise" mode: phase retrieval is precision-sensitive) around small HIP kernels for polar <-> rectangular conversion,
@@ -255,9 +256,11 @@ class GriffinLim:
         self._bb = None
         self._win = win
         self._ft = None
-        # FFT path for power-of-two n_fft (S2ST_GL_FFT=0: the dense-basis GEMMs of rounds 1 - 3, an A/B switch)
+        # FFT path for the n_fft the LDS FFT kernels have a plan for: 256 ... 2048 (powers of two) and the mixed-radix sizes
+        # 240 / 400 / 1200 -- 1200 is what stage 3 writes into config.yaml (S2ST_GL_FFT=0: the dense-basis GEMMs of rounds
+        # 1 - 3, an A/B switch; they also serve every other n_fft)
         import os
-        fn = bd.lib().s2st_gl_fft_supported_i32
+        fn = bd.lib().s2st_fft_len_supported_i32
         self.use_fft = bool(fn(int(n_fft))) and os.environ.get("S2ST_GL_FFT", "1") != "0"
 
     def set_inflight(self, n: int):

@@ -8,12 +8,14 @@ Seeded audio (tests/audio_feat_synth.signal) whose lengths are the bench corpus'
 source utterances of ``src_n_frames`` filter-bank frames at 16 kHz, target utterances of ``tgt_n_frames`` x 300 samples at
 24 kHz.  Three parts:
   1. kernel only: the batch already on the device, device events around --inner back-to-back calls (each call: the
-     offsets scan + the kernels of the route), the three routes in turn per repeat (alternating runs), median and range of
+     offsets scan + the kernels of the route), the routes in turn per repeat (alternating runs), median and range of
      the per-call time; audio-seconds per second, and the bytes the kernel has to move (valid samples in,
      feature rows out) per second against the HBM peak;
   2. the stage end to end (``preprocessing.get_feature_manifest``: PCM files -> data directory) with --extractor device and
   3. the same corpus with --extractor host, alternating, wall clock; and the time of reading the files alone.
-Also the dense route's error against the reference golden (tests/golden/audio_features.npz), as the test prints it.
+The stage's default n_fft 1200 is timed through the mixed-radix FFT kernel (the default) and through the dense bf16x3 product
+(``DeviceFeatureExtractor(fft=False)``: what this size took before the FFT kernels had a plan for it).
+Also both routes' error at n_fft 1200 against the reference golden (tests/golden/audio_features.npz), as the tests print it.
 """
 import argparse
 import importlib
@@ -77,11 +79,13 @@ def main():
 
     # ---- 1. kernel only ----------------------------------------------------------------------------------------------
     ex = fx.DeviceFeatureExtractor(dev, max_samples=1 << 40)  # one batch: the whole corpus
-    forms = [("fbank 16 kHz (512-point FFT)", src16, 16000, None),
-             ("log-mel n_fft 2048 win 1200 hop 300 (FFT)", tgt, 24000, (2048, 1200, 300, 80, 20, 8000)),
-             ("log-mel n_fft 1200 win 1024 hop 300 (dense)", tgt, 24000, (1200, 1024, 300, 80, 20, 8000))]
+    ex_dense = fx.DeviceFeatureExtractor(dev, max_samples=1 << 40, fft=False)
+    forms = [("fbank 16 kHz (512-point FFT)", src16, 16000, None, ex),
+             ("log-mel n_fft 2048 win 1200 hop 300 (FFT)", tgt, 24000, (2048, 1200, 300, 80, 20, 8000), ex),
+             ("log-mel n_fft 1200 win 1024 hop 300 (FFT)", tgt, 24000, (1200, 1024, 300, 80, 20, 8000), ex),
+             ("log-mel n_fft 1200 win 1024 hop 300 (dense)", tgt, 24000, (1200, 1024, 300, 80, 20, 8000), ex_dense)]
     runs = []
-    for name, waves, sr, lm in forms:
+    for name, waves, sr, lm, ex in forms:
         captured = {}
         orig = ex._run
 
@@ -119,15 +123,16 @@ def main():
             f"{100.0 * nbytes / m / HBM_PEAK:11.2f}%")
     say("# (bytes: valid samples read + feature rows written; the dense route also moves its bf16x3 frames and the spectrum)")
 
-    # ---- the dense route's error against the reference golden --------------------------------------------------------------
+    # ---- both routes' error at n_fft 1200 against the reference golden ------------------------------------------------------
     golden = np.load(os.path.join(ROOT, "tests", "golden", "audio_features.npz"))
     g = AS.LOGMEL_DENSE_GEOMETRY
     key = AS.geometry_key(g)
-    feats, _ = ex.logmel(AS.logmel_inputs(g), g[3], g[0], g[1], g[2], AS.N_MELS, g[4], g[5])
-    err = max(float(np.abs(a - golden[f"{key}.logmel.{j}"]).max()) for j, a in enumerate(feats))
     say()
-    say(f"# dense route (n_fft 1200) against the reference's extract_logmel_spectrogram, five seeded inputs: max log-domain "
-        f"difference {err:.3e} (bound of the test: 2e-3; the reference's own fp32 error: {float(golden[key + '.ref_f64_err']):.1e})")
+    for route, e_, bound in (("FFT", forms[2][4], "8 x the reference's own fp32 error"), ("dense", ex_dense, "2e-3")):
+        feats, _ = e_.logmel(AS.logmel_inputs(g), g[3], g[0], g[1], g[2], AS.N_MELS, g[4], g[5])
+        err = max(float(np.abs(a - golden[f"{key}.logmel.{j}"]).max()) for j, a in enumerate(feats))
+        say(f"# {route} route (n_fft 1200) against the reference's extract_logmel_spectrogram, five seeded inputs: max log-domain "
+            f"difference {err:.3e} (bound of the test: {bound}; the reference's own fp32 error: {float(golden[key + '.ref_f64_err']):.1e})")
 
     # ---- 2. / 3. the stage end to end ---------------------------------------------------------------------------------
     with tempfile.TemporaryDirectory() as d:
@@ -165,7 +170,7 @@ def main():
     for extractor in ("device", "host"):
         ts = np.array(times[extractor])
         m = float(np.median(ts))
-        say(f"{'--extractor ' + extractor + ' (n_fft 1200: dense route)':<46} {m:10.3f} [{ts.min():.3f} .. {ts.max():.3f}] "
+        say(f"{'--extractor ' + extractor + ' (n_fft 1200)':<46} {m:10.3f} [{ts.min():.3f} .. {ts.max():.3f}] "
             f"{(s_src + s_tgt) / m:11.0f} {args.utts / m:8.1f}")
     say(f"# reading the {2 * args.utts} PCM files alone (page cache warm): {t_read:.3f} s; host threads: "
         f"{os.environ.get('OMP_NUM_THREADS', 'unset')} (OMP_NUM_THREADS), torch {torch.get_num_threads()}")
