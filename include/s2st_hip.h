@@ -107,6 +107,23 @@ int s2st_gemm_streamk_scratch(float* scratch, int64_t floats, void* stream);
  * fairseq/modules/transformer_layer.py:140-162) with K = tokens unsplit.  S2ST_ERR_SHAPE if a problem does not qualify. */
 int s2st_gemm_group_f32(const s2st_gemm_args* list, int32_t n, void* stream);
 
+/* What s2st_gemm_f32 would launch for a bf16 product, without launching it: the decision of csrc/gemm_bf16_plan.h under the
+ * switches now in the environment.  form: 0 register-staged, 1 LDS-DMA ring, 2 4-wave early-release, 3 256 x 256 four-phase,
+ * 4 persistent walk, 5 256 x 128 ring; grouped: 6 ring, 7 4-wave, 8 persistent, 9 persistent on 256 x 128 tiles.  tag: the
+ * launch's name in the profile registry (s2st_profile_report).  error: the code the launch would return before launching
+ * anything (the other fields are then zero).  Persistent and grouped forms: n problems, total tiles, cvec_of[i] = the
+ * epilogue marks of problem i, sk = the stream-K walk. */
+typedef struct {
+  int32_t error, form, bm, bn, splitk, kchunk, tiles_n, use_slab, vec, cvec, grid_x, grid_y, sk, n, total;
+  int32_t cvec_of[8];
+  char tag[104];
+} s2st_gemm_plan_info;
+/* ncu / slots160 (workgroups of the 160 x 128 4-wave form per CU) <= 0: this device's; with both positive no HIP call is
+ * made, so the decision for a 256-CU chip can be asked on any host.  sk_bound: as if a stream-K scratch were bound. */
+int s2st_gemm_plan_f32(const s2st_gemm_args* args, int32_t ncu, int32_t slots160, int32_t sk_bound, s2st_gemm_plan_info* out);
+/* the same for s2st_gemm_group_f32(list, n) */
+int s2st_gemm_group_plan_f32(const s2st_gemm_args* list, int32_t n, int32_t ncu, int32_t slots160, int32_t sk_bound, s2st_gemm_plan_info* out);
+
 /* Fused multi-head attention (bf16 operands, head width 64 or 128): masks + fp32 online softmax +
  * dropout + P*V in one kernel; backward recomputes the probabilities from the saved log-sum-exp.
  * Replaces fairseq/modules/multihead_attention.py:224-367 (and the same steps inside

@@ -331,6 +331,14 @@ int s2st_gemm_group_f32(const s2st_gemm_args* list, int32_t n, void* stream) {
     if (!s2st_gemm_group_ok(list[i])) return S2ST_ERR_SHAPE;
   return s2st_gemm_bf16_group(list, n, (hipStream_t)stream);
 }
+int s2st_gemm_plan_f32(const s2st_gemm_args* a, int32_t ncu, int32_t slots160, int32_t sk_bound, s2st_gemm_plan_info* out) {
+  if (!a || !out) return S2ST_ERR_ARG;
+  return s2st_gemm_bf16_plan(a, 0, ncu, slots160, sk_bound != 0, out);
+}
+int s2st_gemm_group_plan_f32(const s2st_gemm_args* list, int32_t n, int32_t ncu, int32_t slots160, int32_t sk_bound, s2st_gemm_plan_info* out) {
+  if (!list || n <= 0 || !out) return S2ST_ERR_ARG;
+  return s2st_gemm_bf16_plan(list, n, ncu, slots160, sk_bound != 0, out);
+}
 int s2st_log_softmax_rows_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int32_t rows, int32_t V, int32_t log_out, void* stream) {
   return s2st_log_softmax_rows(x, ldx, y, ldy, rows, V, log_out, (hipStream_t)stream);
 }

@@ -22,6 +22,7 @@
 // Workgroup ids are remapped so that the blocks that share an XCD (id % 8) own a contiguous run
 // of tiles (same A rows -> hits in that XCD's L2).
 #include "gemm_bf16_tile.h"
+#include "gemm_bf16_launch.h"
 
 namespace {
 
@@ -371,82 +372,26 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_dma_group_kernel(GemmGroup 
                                                     grp.xcd_global ? 0 : grp.tile0[pi + 1] - grp.tile0[pi], 0);
 }
 
-// as-launched work of one GEMM (profiling records): FLOPs, and the bytes it has to move at least -- both bf16
-// operands once, the result once per output copy, the old value / residual once when it is read
-double gemm_flops(const GemmArgs& g) { return 2.0 * g.M * g.N * (double)g.K * g.batch; }
-double gemm_min_bytes(const GemmArgs& g) {
-  const double mn = (double)g.M * g.N * g.batch;
-  return 2.0 * g.batch * ((double)g.M * g.K + (double)g.N * g.K) + mn * ((g.C.p ? 4 : 0) + (g.C.h ? 2 : 0)) +
-         mn * 4 * ((g.ep.accumulate ? 1 : 0) + (g.ep.resid ? 1 : 0));
-}
-// profiling tag of an instantiation, spelled like the kernel name in a rocprofv3 kernel trace
-template <int BM, int BN, bool AKM, bool BKM, int NS, int NW, bool IL = false>
-const char* dma_tag() {
-  static char buf[96];
-  if (!buf[0])
-    snprintf(buf, sizeof buf, "gemm_bf16_dma_kernel<%d, %d, %s, %s, %d, %d, %s>", BM, BN, AKM ? "true" : "false",
-             BKM ? "true" : "false", NS, NW, IL ? "true" : "false");
-  return buf;
-}
-template <int BM, int BN, bool AKM, bool BKM, bool VEC>
-const char* staged_tag() {
-  static char buf[80];
-  if (!buf[0])
-    snprintf(buf, sizeof buf, "gemm_bf16_kernel<%d, %d, %s, %s, %s>", BM, BN, AKM ? "true" : "false",
-             BKM ? "true" : "false", VEC ? "true" : "false");
-  return buf;
+// 8-wave LDS-DMA ring form on BM x BN tiles (ring_ns / ring_nw / ring_il name the one instantiation built per tile)
+template <int BM, int BN>
+int launch_ring(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  constexpr int NS = ring_ns(BM), NW = ring_nw(BM), LDS = NS * (dma_a_rows<BM, NW>() + BN) * 128;
+  return with_layouts<dma_a_rows<BM, NW>() == BM>(g, [&](auto a, auto b) {  // (160-row tiles: K-contiguous A only)
+    constexpr bool AKM = decltype(a)::value, BKM = decltype(b)::value;
+    return launch_configured<BM == 256 ? GEMM_RING_256x128 : GEMM_RING, BM, BN, AKM, BKM, false>(
+        gemm_bf16_dma_kernel<BM, BN, AKM, BKM, NS, NW, ring_il(BM)>, LDS, grid, 64 * NW, st, g);
+  });
 }
 
-template <int BM, int BN, int NS, int NW, bool IL = false>
-int launch_dma(const GemmArgs& g, dim3 grid, hipStream_t st) {
-  constexpr int LDS = NS * (dma_a_rows<BM, NW>() + BN) * 128;
-  auto go = [&](auto kern, const char* tag) {
-    static bool configured = false;  // one flag per instantiation (the lambda's operator() template)
-    if (!configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return -1;
-      configured = true;
-    }
-    s2st_launch(tag, gemm_flops(g), gemm_min_bytes(g), kern, grid, dim3(64 * NW), LDS, st, g);
-    return 0;
-  };
-  if (g.A.kmajor && g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, true, true, NS, NW, IL>, dma_tag<BM, BN, true, true, NS, NW, IL>());
-  if (g.A.kmajor && !g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, true, false, NS, NW, IL>, dma_tag<BM, BN, true, false, NS, NW, IL>());
-  if constexpr (dma_a_rows<BM, NW>() == BM) {  // (160-row tiles: K-contiguous A only)
-    if (!g.A.kmajor && g.B.kmajor) return go(gemm_bf16_dma_kernel<BM, BN, false, true, NS, NW, IL>, dma_tag<BM, BN, false, true, NS, NW, IL>());
-    return go(gemm_bf16_dma_kernel<BM, BN, false, false, NS, NW, IL>, dma_tag<BM, BN, false, false, NS, NW, IL>());
-  }
-  return -1;
+int launch_group_ring(const GemmGroup& grp, hipStream_t st) {
+  constexpr int NS = ring_ns(128), NW = ring_nw(128), LDS = NS * (128 + 128) * 128;
+  return with_layouts(grp, [&](auto a, auto b) {
+    constexpr bool AKM = decltype(a)::value, BKM = decltype(b)::value;
+    return launch_configured<GEMM_GROUP_RING, 128, 128, AKM, BKM, false>(
+        gemm_bf16_dma_group_kernel<128, 128, AKM, BKM, NS, NW, true>, LDS, dim3(grp.total < 1 ? 1 : grp.total), 64 * NW, st, grp);
+  });
 }
 
-template <int BM, int BN, int NS, int NW, bool IL = false>
-int launch_dma_group(const GemmGroup& grp, hipStream_t st) {
-  constexpr int LDS = NS * (BM + BN) * 128;
-  double fl = 0, by = 0;
-  for (int i = 0; i < grp.n; ++i) { fl += gemm_flops(grp.g[i]); by += gemm_min_bytes(grp.g[i]); }
-  auto go = [&](auto kern, const char* tag) {
-    static bool configured = false;
-    if (!configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return -1;
-      configured = true;
-    }
-    s2st_launch(tag, fl, by, kern, dim3(grp.total < 1 ? 1 : grp.total), dim3(64 * NW), LDS, st, grp);
-    return 0;
-  };
-  const bool akm = grp.g[0].A.kmajor != 0, bkm = grp.g[0].B.kmajor != 0;
-  static char tags[4][96];
-  auto tag = [&](int i) {
-    if (!tags[i][0])
-      snprintf(tags[i], sizeof tags[i], "gemm_bf16_dma_group_kernel<%d, %d, %s, %s, %d, %d, %s>", BM, BN, (i & 2) ? "true" : "false",
-               (i & 1) ? "true" : "false", NS, NW, IL ? "true" : "false");
-    return (const char*)tags[i];
-  };
-  if (akm && bkm) return go(gemm_bf16_dma_group_kernel<BM, BN, true, true, NS, NW, IL>, tag(3));
-  if (akm && !bkm) return go(gemm_bf16_dma_group_kernel<BM, BN, true, false, NS, NW, IL>, tag(2));
-  if (!akm && bkm) return go(gemm_bf16_dma_group_kernel<BM, BN, false, true, NS, NW, IL>, tag(1));
-  return go(gemm_bf16_dma_group_kernel<BM, BN, false, false, NS, NW, IL>, tag(0));
-}
 
 // The persistent tile walk, its stream-K form and the 256 x 128 tile were built and measured in rounds 2 - 3 (DESIGN.md
 // section 4 / 5: none of them is what the launcher picks for this step's products).  They are compiled only into
@@ -791,37 +736,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_dma_persistent_kernel(GemmG
   }
 }
 
-template <int BM, int BN, bool AKM, bool BKM, int NS, int NW>
-const char* persistent_tag() {
-  static char buf[96];
-  if (!buf[0])
-    snprintf(buf, sizeof buf, "gemm_bf16_dma_persistent_kernel<%d, %d, %s, %s, %d, %d, false>", BM, BN, AKM ? "true" : "false",
-             BKM ? "true" : "false", NS, NW);
-  return buf;
-}
-
-template <int BM, int BN, bool AKM, bool BKM, int NS, int NW>
-const char* streamk_tag() {
-  static char buf[104];
-  if (!buf[0])
-    snprintf(buf, sizeof buf, "gemm_bf16_dma_persistent_kernel<%d, %d, %s, %s, %d, %d, true>", BM, BN, AKM ? "true" : "false",
-             BKM ? "true" : "false", NS, NW);
-  return buf;
-}
 
 #endif  // S2ST_EXPERIMENTAL
 
-// S2ST_GEMM_DMA=0: the register-staged kernel everywhere (no LDS-DMA ring) -- the A/B switch of round 1, read once
-int gemm_dma_enabled() {
-  static const int v = s2st_env_int("S2ST_GEMM_DMA", 1);
-  return v;
-}
-
-int num_cus() {
+// CUs the tile pickers price rounds over and the persistent forms launch on
+int num_cus(const GemmSwitches& sw) {
   // per device (a process drives one GPU, but which one is hipSetDevice's business, not device 0's: VERDICT r5 item 7c)
   static int n[16] = {0};
-  static const int forced = s2st_env_int("S2ST_GEMM_PERSIST_WGS", 0) > 0 ? s2st_env_int("S2ST_GEMM_PERSIST_WGS", 0) : 0;  // tuning aid
-  if (forced) return forced;
+  if (sw.persist_wgs > 0) return sw.persist_wgs;  // tuning aid
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
   if (!n[dev]) {
@@ -833,84 +755,42 @@ int num_cus() {
 }
 
 // ---- stream-K scratch per stream (bound by the training engine for its two streams at the start of a step) ----------
-struct SkScratch { hipStream_t st; float* p; long floats; };
+struct SkScratch { hipStream_t st; float* p; };
 SkScratch g_sk[4];
 int g_sk_n = 0;
 int g_sk_epoch = 0;
+float* sk_scratch(hipStream_t st) {
+  for (int i = 0; i < g_sk_n; ++i) if (g_sk[i].st == st) return g_sk[i].p;
+  return nullptr;
+}
 
-// S2ST_GEMM_STREAMK: 0 = whole tiles per workgroup, 1 = stream-K where a scratch buffer is bound to the stream.  On by
-// default for callers that bind a scratch themselves (s2st_gemm_streamk_scratch); the training engine binds one only
-// with S2ST_GEMM_STREAMK=1 in the environment: measured on MI355X (tools/streamk_probe.py) the
-// hand-off -- L2 write-back behind the release, invalidate + 64 KB read behind the acquire -- costs 12-20 us per launch,
-// more than the idle last round of the 25-45 us products of a training step; it pays from ~2 rounds of long-K tiles on.
 #ifdef S2ST_EXPERIMENTAL
-int streamk_mode() {
-  const char* ev = s2st_env_str("S2ST_GEMM_STREAMK");
-  return ev ? atoi(ev) : 1;
-}
-
-template <int BM, int BN, int NS, int NW>
-int launch_persistent(const GemmGroup& grp_in, hipStream_t st) {
-  constexpr int LDS = NS * (BM + BN) * 128;
-  GemmGroup grp = grp_in;
-  // stream-K when a scratch buffer is bound to this stream and the split pays: uneven rounds of whole tiles (or fewer
-  // tiles than CUs) and enough K-steps per workgroup that the partial-sum hand-off (64 KB out, 64 KB in) is small change
-  grp.sk = 0;
-  if (streamk_mode() > 0 && BM * BN == 128 * 128 && grp.total > 0) {
-    SkScratch* sc = nullptr;
-    for (int i = 0; i < g_sk_n; ++i) if (g_sk[i].st == st && g_sk[i].p) sc = &g_sk[i];
-    long steps = 0;
-    for (int i = 0; i < grp.n; ++i) steps += (long)(grp.tile0[i + 1] - grp.tile0[i]) * ((grp.g[i].K + BK - 1) / BK);
-    const int G = num_cus() & ~7;
-    const long rounds = (grp.total + G - 1) / G;
-    const double waste = 1.0 - (double)grp.total / (double)(rounds * G);  // idle share of the last round
-    const int min_steps = s2st_env_int("S2ST_STREAMK_MIN_STEPS", 8);
-    if (sc && G >= 8 && G <= S2ST_STREAMK_MAX_WGS && waste > 0.08 && steps >= (long)min_steps * G &&
-        sc->floats >= S2ST_STREAMK_SCRATCH_FLOATS) {
-      grp.sk = 1;
-      grp.epoch = ++g_sk_epoch;
-      if (g_sk_epoch > (1 << 30)) g_sk_epoch = 0;
-      grp.sk_ctr = reinterpret_cast<int*>(sc->p);
-      grp.sk_flag = reinterpret_cast<int*>(sc->p) + 16;
-      grp.sk_part = sc->p + 1024;
-    }
-  }
-  double fl = 0, by = 0;
-  for (int i = 0; i < grp.n; ++i) { fl += gemm_flops(grp.g[i]); by += gemm_min_bytes(grp.g[i]); }
-  // S2ST_GROUP_WGS=<n> (tuning aid): cap for grouped launches, which share the chip with the data-path stream
-  constexpr int group_cap = 0;  // (round 2's S2ST_GROUP_WGS: capping the weight-gradient launch to fewer CUs made it the critical path)
-  const int cap = (grp.n > 1 && group_cap > 0) ? group_cap : num_cus();
-  const int grid = grp.sk ? (num_cus() & ~7) : (grp.total < 1 ? 1 : (grp.total < cap ? grp.total : cap));  // (preload: no tiles)
-  auto go = [&](auto kern, const char* tag) {
-    static bool configured = false;
-    if (!configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return -1;
-      configured = true;
-    }
-    s2st_launch(tag, fl, by, kern, dim3(grid), dim3(64 * NW), LDS, st, grp);
-    return 0;
-  };
-  const bool akm = grp.g[0].A.kmajor != 0, bkm = grp.g[0].B.kmajor != 0;
+// grp: the plan's tile list; sk: its stream-K verdict (a scratch is bound to st); grid_x: persistent_grid()
+template <int BM, int BN>
+int launch_persistent(GemmGroup grp, bool sk, int grid_x, hipStream_t st) {
+  constexpr int NS = ring_ns(BM), NW = ring_nw(BM), LDS = NS * (BM + BN) * 128;
+  float* scratch = sk_scratch(st);
+  grp.sk = sk && scratch && BM * BN == 128 * 128;
   if (grp.sk) {
-    if constexpr (BM == 128 && BN == 128) {
-      if (akm && bkm) return go(gemm_bf16_dma_persistent_kernel<BM, BN, true, true, NS, NW, true>, streamk_tag<BM, BN, true, true, NS, NW>());
-      if (akm && !bkm) return go(gemm_bf16_dma_persistent_kernel<BM, BN, true, false, NS, NW, true>, streamk_tag<BM, BN, true, false, NS, NW>());
-      if (!akm && bkm) return go(gemm_bf16_dma_persistent_kernel<BM, BN, false, true, NS, NW, true>, streamk_tag<BM, BN, false, true, NS, NW>());
-      return go(gemm_bf16_dma_persistent_kernel<BM, BN, false, false, NS, NW, true>, streamk_tag<BM, BN, false, false, NS, NW>());
-    }
+    grp.epoch = ++g_sk_epoch;
+    if (g_sk_epoch > (1 << 30)) g_sk_epoch = 0;
+    grp.sk_ctr = reinterpret_cast<int*>(scratch);
+    grp.sk_flag = reinterpret_cast<int*>(scratch) + 16;
+    grp.sk_part = scratch + 1024;
   }
-  if (akm && bkm) return go(gemm_bf16_dma_persistent_kernel<BM, BN, true, true, NS, NW>, persistent_tag<BM, BN, true, true, NS, NW>());
-  if (akm && !bkm) return go(gemm_bf16_dma_persistent_kernel<BM, BN, true, false, NS, NW>, persistent_tag<BM, BN, true, false, NS, NW>());
-  if (!akm && bkm) return go(gemm_bf16_dma_persistent_kernel<BM, BN, false, true, NS, NW>, persistent_tag<BM, BN, false, true, NS, NW>());
-  return go(gemm_bf16_dma_persistent_kernel<BM, BN, false, false, NS, NW>, persistent_tag<BM, BN, false, false, NS, NW>());
+  return with_layouts(grp, [&](auto a, auto b) {
+    constexpr bool AKM = decltype(a)::value, BKM = decltype(b)::value;
+    if constexpr (BM == 128 && BN == 128) {
+      if (grp.sk)
+        return launch_configured<GEMM_PERSISTENT, BM, BN, AKM, BKM, true>(
+            gemm_bf16_dma_persistent_kernel<BM, BN, AKM, BKM, NS, NW, true>, LDS, dim3(grid_x), 64 * NW, st, grp);
+    }
+    return launch_configured<GEMM_PERSISTENT, BM, BN, AKM, BKM, false>(
+        gemm_bf16_dma_persistent_kernel<BM, BN, AKM, BKM, NS, NW>, LDS, dim3(grid_x), 64 * NW, st, grp);
+  });
 }
-
-#else
-int streamk_mode() { return 0; }
-template <int BM, int BN, int NS, int NW>
-int launch_persistent(const GemmGroup&, hipStream_t) { return S2ST_ERR_ARG; }  // (not built: never reached, see persist_mode())
 #endif  // S2ST_EXPERIMENTAL
+
 
 // C(m, n) (+)= sum_s slab[z][s][m][n]
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, GemmOut C, int M, int N,
@@ -944,74 +824,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+// register-staged form (operands the LDS-DMA kernels cannot take, or S2ST_GEMM_DMA=0)
 template <int BM, int BN, bool VEC>
-void launch_layouts(const GemmArgs& g, dim3 grid, hipStream_t st) {
-  const double fl = gemm_flops(g), by = gemm_min_bytes(g);
-  if (g.A.kmajor && g.B.kmajor)
-    s2st_launch(staged_tag<BM, BN, true, true, VEC>(), fl, by, gemm_bf16_kernel<BM, BN, true, true, VEC>, grid, dim3(256), 0, st, g);
-  else if (g.A.kmajor && !g.B.kmajor)
-    s2st_launch(staged_tag<BM, BN, true, false, VEC>(), fl, by, gemm_bf16_kernel<BM, BN, true, false, VEC>, grid, dim3(256), 0, st, g);
-  else if (!g.A.kmajor && g.B.kmajor)
-    s2st_launch(staged_tag<BM, BN, false, true, VEC>(), fl, by, gemm_bf16_kernel<BM, BN, false, true, VEC>, grid, dim3(256), 0, st, g);
-  else
-    s2st_launch(staged_tag<BM, BN, false, false, VEC>(), fl, by, gemm_bf16_kernel<BM, BN, false, false, VEC>, grid, dim3(256), 0, st, g);
-}
-
-// 16-byte fast path: aligned base, ld and batch strides multiples of 8 elements.  (K tails are
-// masked in the kernel; rows-contiguous operands rely on the padded-row contract.)
-bool vec_ok(const GemmOperand& o) {
-  return ((uintptr_t)o.p % 16 == 0) && (o.sp.ld % 8 == 0) && (o.sp.bs % 8 == 0) && (o.zo % 8 == 0) &&
-         (o.zi % 8 == 0);
-}
-
-bool dma_layout_ok(const GemmArgs& g) { return (g.A.kmajor || g.A.sp.per <= 0) && (g.B.kmajor || g.B.sp.per <= 0); }
-
-// alignment flags the kernels / epilogue read; returns whether the 16-byte operand path applies
-bool prep_flags(GemmArgs& g) {
-  const bool vec = vec_ok(g.A) && vec_ok(g.B);
-  g.avec = g.bvec = vec ? 1 : 0;
-  g.cvec = ((!g.C.p || (uintptr_t)g.C.p % 16 == 0) && (!g.C.h || (uintptr_t)g.C.h % 8 == 0) &&
-            g.C.sp.ld % 4 == 0 && g.C.sp.bs % 4 == 0 && g.C.zo % 4 == 0 && g.C.zi % 4 == 0 &&
-            (!g.ep.resid || (uintptr_t)g.ep.resid % 16 == 0) && (!g.ep.bias || ((uintptr_t)g.ep.bias % 16 == 0 && g.ep.bias_zo % 4 == 0)))
-               ? 1 : 0;
-  return vec;
-}
-
-// bit 1 of cvec: the straight-line epilogue applies (gemm_epilogue_fast; S2ST_GEMM_FAST_EPI=0 is the A/B switch).
-// Called once split-K / slab decisions are made.
-void mark_fast_epilogue(GemmArgs& g) {
-  g.cvec &= 1;  // (bits 1 .. 3 are set below)
-  const char* ev = s2st_env_str("S2ST_GEMM_FAST_EPI");
-  if (ev && atoi(ev) == 0) return;
-  const bool drop = g.ep.drop_p > 0.f, res = g.ep.resid != nullptr, accu = g.ep.accumulate != 0;
-  const bool combo = !accu || (!drop && !res && !g.C.h);  // instantiated: {-, resid, drop, drop + resid} x outputs, accumulate (fp32)
-  // the bf16 copy is stored 16 bytes (8 columns) per lane
-  const bool h16 = !g.C.h || ((uintptr_t)g.C.h % 16 == 0 && g.C.sp.ld % 8 == 0 && g.C.sp.bs % 8 == 0 && g.C.zo % 8 == 0 &&
-                              g.C.zi % 8 == 0 && g.N % 8 == 0);
-  if (g.cvec && g.N >= 4 && g.N % 4 == 0 && g.M >= 1 && g.splitk == 1 && !g.slab && !g.ep.mask_y && !g.ep.colsum && !g.ep.colsum_part &&
-      (g.ep.act != 2 || (!drop && !accu)) && combo && h16 && (g.C.p || g.C.h) && (!accu || g.C.p))
-    g.cvec |= 2;
-  // bit 3: the masked data-gradient form (bf16 output only, nothing else in the epilogue but the column sums)
-  if (g.cvec && g.ep.mask_y && g.C.h && !g.C.p && h16 && g.N >= 8 && g.M >= 1 && g.splitk == 1 && !g.slab && !g.ep.bias &&
-      g.ep.act == 0 && !drop && !res && !accu && (uintptr_t)g.ep.mask_y % 16 == 0)
-    g.cvec |= 8;
-}
-
-// S2ST_GEMM_PERSIST: 0 = one-shot kernels only, 1 = grouped launches persistent, single products one-shot (default:
-// with more tiles than CUs the hardware dispatcher back-fills CUs as one-shot workgroups retire, which balances better
-// than a fixed walk of 2.25 tiles per workgroup -- 10.05 vs 10.58 ms per training step, profiles/r02_ab_switches.txt),
-// 2 = every 128-row launch persistent, 3 = grouped launches and single products with more tiles than CUs
-// CUs a single product's tiles are priced over (the tile pickers' round counts)
-int data_cus() { return num_cus(); }
-
-int persist_mode() {
-  const char* ev = s2st_env_str("S2ST_GEMM_PERSIST");  // read per call: an A/B switch the tests flip
-  const int v = ev ? atoi(ev) : 1;
-#ifdef S2ST_EXPERIMENTAL
-  return v;
-#else
-  return v > 1 ? 1 : v;  // (2 / 3 need the persistent kernels: experimental builds only)
-#endif
+int launch_staged(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  return with_layouts(g, [&](auto a, auto b) {
+    constexpr bool AKM = decltype(a)::value, BKM = decltype(b)::value;
+    return launch_configured<GEMM_STAGED, BM, BN, AKM, BKM, VEC>(gemm_bf16_kernel<BM, BN, AKM, BKM, VEC>, 0, grid, 256, st, g);
+  });
 }
 
 constexpr bool kExperimental =
@@ -1020,329 +839,167 @@ constexpr bool kExperimental =
 #else
     false;
 #endif
+static_assert(GEMM_BK == BK, "the plan prices the kernels' K-step");
 
-// S2ST_GEMM_W4 (read per call: an A/B switch): 0 = the 8-wave ring kernels only (one workgroup per CU); -1 (default) =
-// the 4-wave early-release form (gemm_bf16_w4.hip, 2 - 3 workgroups per CU) for single products with at least one
-// 128 x 128 tile per CU, see w4_pick(); 1 = every 128-row single product on it; 2 = grouped weight gradients too
-int w4_mode() {
-  const char* ev = s2st_env_str("S2ST_GEMM_W4");
-  return ev ? atoi(ev) : -1;
-}
-
-// Which form runs a single product (measured per shape on MI355X with tools/gemm_forms_bench.py, kernel time from
-// events attached to the dispatch, profiles/r03_gemm_forms.txt).  With fewer 128 x 128 tiles than CUs (M ~ 4.6 k tokens x
-// N = 512: 144 tiles) nothing co-resides anyway and the 8-wave kernel's faster K-loop wins (17.5 vs 23.9 us at K = 2048);
-// from one tile per CU on, two or three co-resident workgroups hide each other's prologue / epilogue / barrier waits:
-// N = 1536 ... 2048 at K = 512 run 10 - 30 % shorter (4584 x 2048 x 512: 17.5 vs 21.4 us; 2800 x 1536 x 512: 11.1 vs 15.8).
-// Between the two 4-wave shapes the fuller last round wins: 128 x 128 tiles over 2 slots per CU against 128 x 64 tiles
-// over 3 (the pick agreed with the faster of the two on every measured shape).
-// Round 8, 160 x 128 tiles (K-contiguous A): the same rounds-of-slots count.  Where the 128-row pick needs a second round
-// and 160-row tiles fit the chip's slots in ONE (N = 2048 with 4096 < M <= 5120: 33 - 40 row tiles x 16 against 512 slots,
-// <= 32 x 16 with 160 rows), one round of 1.25x tiles beats 1.1 - 1.25 rounds: 23.0 -> 17.7 us was the step at M = 4096
-// (profiles/r06_gemm_m_sweep.txt; tools/gemm_m_sweep.py now runs to M = 5120).  With one
-// round either way (M <= 4096; N = 1536) the smaller tile stays, and products of many rounds are not touched.
-// Returns 0 (8-wave kernels), else bn of the 4-wave form; *bm gets its tile rows (128 or 160).
-bool tile160_ok(const GemmArgs& g) { return g.A.kmajor && g.A.sp.per <= 0 && g.batch == 1; }
-
-int w4_pick(const GemmArgs& g, bool dma_ok, int* bm) {
-  *bm = 128;
-  const int mode = w4_mode();
-  if (mode == 0 || !dma_ok || g.M < 128) return 0;
-  const long tm = (g.M + 127) / 128;
-  const long t128 = tm * ((g.N + 127) / 128) * g.batch, t64 = tm * ((g.N + 63) / 64) * g.batch;
-  if (mode < 0 && t128 < data_cus()) return 0;
-  const long s128 = 2L * data_cus(), s64 = 3L * data_cus();
-  const double e128 = (double)t128 / (double)(((t128 + s128 - 1) / s128) * s128);
-  const double e64 = (double)t64 / (double)(((t64 + s64 - 1) / s64) * s64);
-  if (tile160_ok(g) && g.N > 64) {
-    const long t160 = (long)((g.M + 159) / 160) * ((g.N + 127) / 128);
-    const long s160 = (long)s2st_gemm_bf16_w4_slots160() * data_cus();
-    if (t160 <= s160 && t128 > s128 && t64 > s64) { *bm = 160; return 128; }
+// The switches a call of `scope` looks at, from the environment: S2ST_GEMM_DMA, S2ST_SPLITK_TARGET and S2ST_GEMM_PERSIST_WGS
+// once per process, the others per call (A/B switches the tests flip) -- each of them once.
+enum SwitchScope { SW_MEMBER, SW_GROUP, SW_SINGLE };
+GemmSwitches gemm_switches(SwitchScope scope) {
+  static const int dma = s2st_env_int("S2ST_GEMM_DMA", 1), target = s2st_env_int("S2ST_SPLITK_TARGET", 128),
+                   wgs = s2st_env_int("S2ST_GEMM_PERSIST_WGS", 0);
+  GemmSwitches sw;
+  sw.dma = dma;
+  sw.splitk_target = target;
+  sw.persist_wgs = wgs;
+  sw.persist = s2st_env_int("S2ST_GEMM_PERSIST", sw.persist);
+  if (!kExperimental && sw.persist > 1) sw.persist = 1;  // (2 / 3 need the persistent kernels: experimental builds only)
+  if (scope == SW_MEMBER) return sw;
+  sw.w4 = s2st_env_int("S2ST_GEMM_W4", sw.w4);
+  sw.fast_epi = s2st_env_int("S2ST_GEMM_FAST_EPI", 1) != 0;
+  sw.streamk = kExperimental ? s2st_env_int("S2ST_GEMM_STREAMK", 1) : 0;  // (stream-K: experimental builds only)
+  if (sw.streamk > 0) sw.streamk_min_steps = s2st_env_int("S2ST_STREAMK_MIN_STEPS", sw.streamk_min_steps);
+  if (scope == SW_GROUP) {
+    sw.group_tile = s2st_env_int("S2ST_GROUP_TILE", 0);
+    sw.group_oneshot = s2st_env_int("S2ST_GROUP_ONESHOT", 1) != 0;
+    return sw;
   }
-  // Round 5: many rounds of long K-loops are priced by the steady state, not by the last round's fill -- per flop the
-  // 128 x 128 tile needs 2/3 of the LDS reads of the 128 x 64 one.  HuBERT's conv stack (307 k / 154 k rows x 512 x 1536):
-  // 632 vs 750 us and 342 vs 402 us, where the fill rule took 128 x 64 (25.0 full rounds against 18.75);
-  // tools/conv_forms_bench.py, profiles/r05_hubert_forms.txt.  (The training step's products have < 4 rounds: unchanged.)
-  if (g.N > 64 && g.K >= 1024 && t128 >= 4 * s128) return 128;
-  return (g.N > 64 && e128 >= e64) ? 128 : 64;
+  sw.p4 = s2st_env_int("S2ST_GEMM_P4", sw.p4);
+  if (const char* force = s2st_env_str("S2ST_GEMM_TILE")) {
+    sw.tile_set = true;
+    if (sscanf(force, "%dx%d", &sw.tile_bm, &sw.tile_bn) != 2) sw.tile_bm = sw.tile_bn = 64;
+  }
+  return sw;
 }
 
-// S2ST_GEMM_P4 (read per call: an A/B switch): 0 = never; -1 (default) = the 256 x 256 four-phase form (gemm_bf16_p4.hip)
-// where p4_pick() says so; 1 = every product it can run.  It can run: both operands K-contiguous with plain row strides,
-// 16-byte aligned, batch 1, no split-K, no masked epilogue.  The pick is a two-line cost model fitted to
-// tools/gemm_p4_bench.py (profiles/r05_gemm_p4_bench.txt, random operands, kernel time from events on the dispatch):
-//   four-phase form : rounds of 256-row tiles over the CUs x (2.0 us per 64-deep K-tile + 7 us of prologue / epilogue)
-//   128-row forms   : ~650 TFLOP/s on products of this size (577 - 693 measured; 870 on 4096^3)
-// It takes 4096^3 (126 vs 159 us: 1.09 PFLOP/s), HuBERT's FFN-in products (9600 x 3072 x 768: 64 vs 78 us; 19200 rows: 119 vs
-// 148) and leaves the K = 512 products of the training step (one round of 8 K-tiles: 21 vs 14 - 19 us) and the short-N
-// ones (768 columns: a third of the CUs) where they were.
-int p4_mode() {
-  const char* ev = s2st_env_str("S2ST_GEMM_P4");
-  return ev ? atoi(ev) : -1;
-}
-bool p4_can(const GemmArgs& g, bool dma_ok) {
-  return dma_ok && g.A.kmajor && g.B.kmajor && g.batch == 1 && g.A.sp.per <= 0 && g.B.sp.per <= 0 && !g.ep.mask_y &&
-         !g.ep.colsum && !g.ep.colsum_part;
-}
-bool p4_pick(const GemmArgs& g, bool dma_ok) {
-  const int mode = p4_mode();
-  if (mode == 0 || !p4_can(g, dma_ok)) return false;
-  if (mode >= 1) return true;
-  if (g.M < 512 || g.N < 512 || g.K < 8 * BK) return false;
-  const long tiles = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
-  const long ncu = data_cus();
-  const long rounds = (tiles + ncu - 1) / ncu;
-  const double t_p4 = (double)rounds * (2.0 * ((g.K + BK - 1) / BK) + 7.0);          // us
-  const double t_ring = 2.0 * g.M * (double)g.N * g.K / 650e6;                        // us at 650 TFLOP/s
-  // (0.80, not parity: beside a training step -- HuBERT's front end runs ahead on a second stream -- a 512-thread workgroup
-  // holding 128 KB of LDS for tens of microseconds keeps the step's short dependent kernels off its CU; with the threshold
-  // at 0.92 the front end's FFN-in products took this form, 64 vs 78 us alone, and config 3 / 4 got SLOWER: 10.77 - 11.0
-  // vs 10.63 ms per step, profiles/r05_hubert_p4_ab.txt)
-  return t_p4 < 0.80 * t_ring;
+// ncu / slots160 <= 0: this device's
+GemmChip gemm_chip(const GemmSwitches& sw, int ncu = 0, int slots160 = 0) {
+  return GemmChip{ncu > 0 ? ncu : num_cus(sw), slots160 > 0 ? slots160 : s2st_gemm_bf16_w4_slots160(), kExperimental};
 }
 
-template <int BN, int BM = 128>
-void add_to_group(GemmGroup& grp, GemmArgs g) {
-  g.splitk = 1;
-  g.slab = nullptr;
-  g.kchunk = ((g.K + BK - 1) / BK) * BK;
-  g.tiles_n = (g.N + BN - 1) / BN;
-  mark_fast_epilogue(g);
-  const int i = grp.n++;
-  grp.g[i] = g;
-  grp.tile0[i + 1] = grp.tile0[i] + ((g.M + BM - 1) / BM) * g.tiles_n;
-  grp.total = grp.tile0[i + 1];
+// the kernel argument of a persistent / grouped plan: every problem with the plan's fields filled in
+GemmGroup group_of(const GemmArgs* list, const GemmPlan& p) {
+  GemmGroup grp{};
+  grp.n = p.n;
+  grp.total = p.total;
+  for (int i = 0; i < p.n; ++i) {
+    GemmArgs& g = grp.g[i] = list[i];
+    if (g.zdiv <= 0) g.zdiv = 1;
+    g.avec = g.bvec = p.vec;
+    g.cvec = p.cvec_of[i];
+    g.splitk = 1;
+    g.slab = nullptr;
+    g.kchunk = ((g.K + BK - 1) / BK) * BK;
+    g.tiles_n = (g.N + p.bn - 1) / p.bn;
+    grp.tile0[i + 1] = p.tile0[i + 1];
+  }
+  return grp;
 }
 
 }  // namespace
 
 void s2st_gemm_streamk_bind(hipStream_t st, float* scratch, long floats) {
+  if (floats < S2ST_STREAMK_SCRATCH_FLOATS) scratch = nullptr;  // (too small to share K through: as good as none)
   for (int i = 0; i < g_sk_n; ++i)
-    if (g_sk[i].st == st) { g_sk[i].p = scratch; g_sk[i].floats = floats; return; }
-  if (g_sk_n < 4) g_sk[g_sk_n++] = SkScratch{st, scratch, floats};
+    if (g_sk[i].st == st) { g_sk[i].p = scratch; return; }
+  if (g_sk_n < 4) g_sk[g_sk_n++] = SkScratch{st, scratch};
 }
 void s2st_gemm_streamk_unbind_all() { g_sk_n = 0; }
 
-bool s2st_gemm_group_ok(const GemmArgs& g0) {
-  GemmArgs g = g0;
-  if (g.A.dtype != S2ST_BF16 || g.B.dtype != S2ST_BF16 || g.precise || persist_mode() == 0) return false;
-  static const int use_dma = gemm_dma_enabled();
-  if (!use_dma || !prep_flags(g) || !dma_layout_ok(g) || g.batch != 1 || g.M < 128 || g.N < 128 || g.K < 1) return false;
-  if (g.ep.mask_y && (!g.cvec || g.N % 4 != 0)) return false;
-  return true;
+bool s2st_gemm_group_ok(const GemmArgs& g) {
+  return group_member_ok(g, gemm_switches(SW_MEMBER));
 }
 
 // list[0..n): problems that passed s2st_gemm_group_ok, all with the layouts of list[0]
 int s2st_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t st) {
   if (n <= 0) return 0;
-  if (n > S2ST_GROUP_MAX) return S2ST_ERR_ARG;
-  GemmGroup grp{};
-  for (int i = 0; i < n; ++i) {
-    GemmArgs g = list[i];
-    if (g.zdiv <= 0) g.zdiv = 1;
-    if (!prep_flags(g) || g.A.kmajor != list[0].A.kmajor || g.B.kmajor != list[0].B.kmajor) return S2ST_ERR_ARG;
-    add_to_group<128>(grp, g);
+  const GemmSwitches sw = gemm_switches(SW_GROUP);
+  const GemmPlan p = plan_group(list, n, sw, gemm_chip(sw), sk_scratch(st) != nullptr);
+  if (p.error) return p.error;
+  GemmGroup grp = group_of(list, p);
+  // S2ST_GROUP_XCD=0 (A/B switch): every product's tiles spread over all XCDs (the form up to round 3)
+  grp.xcd_global = 1;  // (one contiguous run of the tile list per XCD: 206 -> 121 MB fetched per launch, round 3)
+  int rc = S2ST_ERR_ARG;
+  switch (p.form) {
+    case GEMM_GROUP_RING: rc = launch_group_ring(grp, st); break;
+    case GEMM_GROUP_W4: rc = s2st_gemm_bf16_w4_group(grp, st); break;
+#ifdef S2ST_EXPERIMENTAL
+    case GEMM_GROUP_PERSISTENT: rc = launch_persistent<128, 128>(grp, p.sk, p.grid_x, st); break;
+    case GEMM_GROUP_PERSISTENT_256: rc = launch_persistent<256, 128>(grp, p.sk, p.grid_x, st); break;
+#endif
+    default: break;
   }
-  // S2ST_GROUP_TILE=256: 256 x 128 tiles (48 KB of operands per K-step for twice the FLOPs: half the workgroups, which
-  // leaves CUs to the data-path stream the group runs beside)
-  const char* gt = s2st_env_str("S2ST_GROUP_TILE");
-  bool big = kExperimental && gt && atoi(gt) == 256;
-  for (int i = 0; i < n && big; ++i) big = list[i].M >= 256;
-  if (big) {
-    GemmGroup g2{};
-    for (int i = 0; i < n; ++i) {
-      GemmArgs g = list[i];
-      if (g.zdiv <= 0) g.zdiv = 1;
-      prep_flags(g);
-      add_to_group<128, 256>(g2, g);
-    }
-    if constexpr (kExperimental) {
-      if (launch_persistent<256, 128, 3, 8>(g2, st)) return S2ST_ERR_LAUNCH;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
-  }
-  // default: one workgroup per tile of the concatenated list (plain K-loop: 9.65 vs 9.76 ms/step);
-  // S2ST_GROUP_ONESHOT=0: the persistent tile walk (also what S2ST_GROUP_TILE=256 and a bound stream-K scratch use)
-  const char* os = s2st_env_str("S2ST_GROUP_ONESHOT");
-  bool sk_bound = false;
-  for (int i = 0; i < g_sk_n; ++i) sk_bound = sk_bound || (g_sk[i].st == st && g_sk[i].p);
-  if (!kExperimental || (!(os && atoi(os) == 0) && !(sk_bound && streamk_mode() > 0))) {
-    // S2ST_GROUP_XCD=0 (A/B switch): every product's tiles spread over all XCDs (the form up to round 3)
-    constexpr bool xcd_global = true;  // (one contiguous run of the tile list per XCD: 206 -> 121 MB fetched per launch, round 3)
-    grp.xcd_global = xcd_global ? 1 : 0;
-    if (w4_mode() >= 2 ? s2st_gemm_bf16_w4_group(grp, st) : launch_dma_group<128, 128, 4, 8, true>(grp, st)) return S2ST_ERR_LAUNCH;
-    return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
-  }
-  if (launch_persistent<128, 128, 4, 8>(grp, st)) return S2ST_ERR_LAUNCH;
-  return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
+  return rc == 0 && hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
 }
 
 // Launch every kernel instantiation once on an empty problem (M = N = K = 0: no loads, no stores) so
 // that code objects are resident and the > 64 KiB dynamic-LDS attribute is set before the first
 // timed step (first use of a kernel on a fresh process costs milliseconds).
 int s2st_gemm_bf16_preload(hipStream_t st) {
-  GemmArgs g{};
-  g.A.dtype = g.B.dtype = S2ST_BF16;
-  g.splitk = 1; g.zdiv = 1; g.tiles_n = 1; g.batch = 1; g.kchunk = BK;
   dim3 grid(1, 1, 1);
   int rc = 0;
   for (int lay = 0; lay < 4; ++lay) {
-    g.A.kmajor = lay & 1; g.B.kmajor = (lay >> 1) & 1;
-    launch_layouts<128, 128, true>(g, grid, st);
-    launch_layouts<128, 64, true>(g, grid, st);
-    launch_layouts<64, 64, true>(g, grid, st);
-    launch_layouts<64, 64, false>(g, grid, st);
-    rc |= launch_dma<128, 128, 4, 8, true>(g, grid, st);
-    rc |= launch_dma<128, 64, 4, 8, true>(g, grid, st);
-    if (g.A.kmajor) rc |= launch_dma<160, 64, 4, 8, true>(g, grid, st);
-    rc |= launch_dma<64, 64, 4, 4, true>(g, grid, st);
+    const GemmArgs g = empty_problem(lay);
+    rc |= launch_staged<128, 128, true>(g, grid, st);
+    rc |= launch_staged<128, 64, true>(g, grid, st);
+    rc |= launch_staged<64, 64, true>(g, grid, st);
+    rc |= launch_staged<64, 64, false>(g, grid, st);
+    rc |= launch_ring<128, 128>(g, grid, st);
+    rc |= launch_ring<128, 64>(g, grid, st);
+    if (g.A.kmajor) rc |= launch_ring<160, 64>(g, grid, st);
+    rc |= launch_ring<64, 64>(g, grid, st);
     GemmGroup grp{};  // no tiles: the kernels fall straight through
     grp.n = 1;
     grp.g[0] = g;
-    if constexpr (kExperimental) {
-      rc |= launch_persistent<128, 128, 4, 8>(grp, st);
-      rc |= launch_persistent<128, 64, 4, 8>(grp, st);
-      rc |= launch_persistent<256, 128, 3, 8>(grp, st);
-      rc |= launch_dma<256, 128, 3, 8>(g, grid, st);
-    }
-    { GemmGroup g0 = grp; g0.total = 0; g0.n = 1; rc |= launch_dma_group<128, 128, 4, 8, true>(g0, st); }
+#ifdef S2ST_EXPERIMENTAL
+    rc |= launch_persistent<128, 128>(grp, false, 1, st);
+    rc |= launch_persistent<128, 64>(grp, false, 1, st);
+    rc |= launch_persistent<256, 128>(grp, false, 1, st);
+    rc |= launch_ring<256, 128>(g, grid, st);
+#endif
+    rc |= launch_group_ring(grp, st);
   }
   rc |= s2st_gemm_bf16_w4_preload(st);
   rc |= s2st_gemm_bf16_p4_preload(st);
   return rc || hipGetLastError() != hipSuccess ? -1 : 0;
 }
 
-// tile choice: estimated time = rounds over the 256 CUs x per-tile work / per-tile efficiency
-int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
-  const bool vec = prep_flags(g);
-  if (g.ep.mask_y && (!g.cvec || g.N % 4 != 0)) return S2ST_ERR_SHAPE;
-  const bool linear_epi = !g.ep.act && g.ep.drop_p == 0.f && !g.ep.mask_y;
-  struct Cand { int bm, bn; double eff; };
-  // (tile-preference weights: round 2's sweep.  160 x 64, round 8: the 128 x 64 kernel with five row blocks per wave, so
-  //  its weight -- a candidate only where it runs in ONE round, K-contiguous A, on the LDS-DMA kernels: N = 512 with
-  //  4096 < M <= 5120, where 128 x 64 needs a second round and the pick used to fall to 144 - 160 tiles of 128 x 128)
-  static const Cand cands[4] = {{128, 128, 1.0}, {128, 64, 0.8}, {160, 64, 0.8}, {64, 64, 0.55}};
-  const bool may_split = g.ep.accumulate && linear_epi && g.C.p && !g.C.h && !g.ep.bias && !g.ep.resid && g.K >= 8 * BK;
-  const bool can160 = vec && gemm_dma_enabled() && dma_layout_ok(g) && tile160_ok(g) && persist_mode() <= 1;
-  static const int splitk_target = s2st_env_int("S2ST_SPLITK_TARGET", 128);
-  int bm = 64, bn = 64;
-  if (vec) {
-    double best = 1e300;
-    for (const Cand& c : cands) {
-      long tiles = (long)((g.M + c.bm - 1) / c.bm) * ((g.N + c.bn - 1) / c.bn) * g.batch;
-      const long ncu = data_cus();
-      long rounds = (tiles + ncu - 1) / ncu;
-      if (c.bm == 160 && !(can160 && rounds == 1 && (!may_split || tiles >= splitk_target))) continue;  // (never a product that would split K)
-      // split-K candidates fill the chip anyway: cost by work / efficiency only
-      double cost = (double)rounds * c.bm * c.bn / c.eff;
-      if (cost < best) { best = cost; bm = c.bm; bn = c.bn; }
-    }
+// One bf16 product: fill the switches, plan (gemm_bf16_plan.h: every decision is there), launch the plan's form
+int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* tile_out) {
+  const GemmSwitches sw = gemm_switches(SW_SINGLE);
+  const GemmPlan p = plan_single(g, sw, gemm_chip(sw), sk_scratch(st) != nullptr);
+  if (p.error) return p.error;
+  g.avec = g.bvec = p.vec;
+  g.cvec = p.cvec;
+  g.splitk = p.splitk;
+  g.kchunk = p.kchunk;
+  g.tiles_n = p.tiles_n;
+  g.slab = p.use_slab ? g.ws : nullptr;
+  if (tile_out) *tile_out = p.bm * 1000 + p.bn;
+  const dim3 grid(p.grid_x, p.grid_y, 1);
+  const bool wide = p.bn == 128;
+  int rc = S2ST_ERR_ARG;
+  switch (p.form) {
+    case GEMM_STAGED:
+      rc = !p.vec ? launch_staged<64, 64, false>(g, grid, st) : p.bm == 64 ? launch_staged<64, 64, true>(g, grid, st)
+           : wide ? launch_staged<128, 128, true>(g, grid, st) : launch_staged<128, 64, true>(g, grid, st);
+      break;
+    case GEMM_RING:
+      rc = p.bm == 160 ? launch_ring<160, 64>(g, grid, st) : p.bm == 64 ? launch_ring<64, 64>(g, grid, st)
+           : wide ? launch_ring<128, 128>(g, grid, st) : launch_ring<128, 64>(g, grid, st);
+      break;
+    case GEMM_W4: rc = s2st_gemm_bf16_w4(g, p.bm, p.bn, grid, st); break;
+    case GEMM_P4: rc = s2st_gemm_bf16_p4(g, grid, st); break;
+#ifdef S2ST_EXPERIMENTAL
+    case GEMM_RING_256x128: rc = launch_ring<256, 128>(g, grid, st); break;
+    case GEMM_PERSISTENT:
+      rc = wide ? launch_persistent<128, 128>(group_of(&g, p), p.sk, p.grid_x, st)
+                : launch_persistent<128, 64>(group_of(&g, p), p.sk, p.grid_x, st);
+      break;
+#endif
+    default: break;
   }
-  if (vec) {  // tuning aid: S2ST_GEMM_TILE=128x128|128x64|64x64 forces the tile
-    const char* force = s2st_env_str("S2ST_GEMM_TILE");  // (read per call: the tests switch it)
-    if (force && sscanf(force, "%dx%d", &bm, &bn) != 2) { bm = 64; bn = 64; }
-    // 160x128 (4-wave form) / 160x64 (8-wave ring form): where the product cannot take them, the 128-row tile of that width
-    if (force && bm == 160 && !(can160 && (bn == 128 || bn == 64))) bm = 128;
-  }
-  const bool can_split_ = may_split && bm != 160;  // a 160-row tile, picked or forced, runs K unsplit
-  const bool forced_p4 = vec && bm == 256 && bn == 256;  // S2ST_GEMM_TILE=256x256: the four-phase form where it can run
-  if (bm == 256 && !forced_p4 && !(kExperimental && vec && dma_layout_ok(g) && g.batch == 1)) { bm = 128; bn = 128; }  // 256-row tiles: ring kernels of experimental builds only
-  if (vec && can_split_ && (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch < 256) { bm = 128; bn = 128; }
-  // the 4-wave early-release form (w4_pick above): a forced tile is honoured (S2ST_GEMM_W4 >= 1 puts it on that form)
-  int w4bn = 0;
-  {
-    static const int use_dma_w4 = gemm_dma_enabled();
-    const bool split_like = can_split_ && (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch < 256;
-    if (vec && use_dma_w4 && dma_layout_ok(g) && !split_like && persist_mode() != 2) {
-      int w4bm = 128;
-      if (s2st_env_str("S2ST_GEMM_TILE")) {
-        if (bm == 160 && bn == 128) { w4bn = 128; w4bm = 160; }  // (the 4-wave form is the only 160 x 128 one)
-        else w4bn = (w4_mode() >= 1 && bm == 128 && (bn == 128 || bn == 64)) ? bn : 0;
-      } else w4bn = w4_pick(g, true, &w4bm);
-      if (w4bn) { bm = w4bm; bn = w4bn; }
-    }
-  }
-  // the 256 x 256 four-phase form (p4_pick above); a forced tile is honoured where the form can run at all
-  bool p4 = false;
-  {
-    static const int use_dma_p4 = gemm_dma_enabled();
-    const bool split_like = can_split_ && (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch < 256;
-    const bool can = vec && use_dma_p4 && !split_like && persist_mode() != 2 && p4_can(g, dma_layout_ok(g));
-    if (s2st_env_str("S2ST_GEMM_TILE")) p4 = forced_p4 && can && p4_mode() != 0;
-    else p4 = can && p4_pick(g, true);
-    if (forced_p4 && !p4) { bm = 128; bn = 128; }
-    if (p4) { bm = 256; bn = 256; w4bn = 0; }
-  }
-  // (a forced 256 x 256 form on a product that then splits K -- fewer than 256 tiles of 256 x 256 -- used to fall
-  //  through to the 64 x 64 launch with a grid built for 256 x 256 tiles: most of C never written.  The four-phase kernel has
-  //  no split-K form, so such a product goes back to 128 x 128 tiles BEFORE the grid is derived.)
-  if (p4 && can_split_ && (long)((g.M + 255) / 256) * ((g.N + 255) / 256) * g.batch < 256) { p4 = false; bm = 128; bn = 128; }
-  const int tm = (g.M + bm - 1) / bm, tn = (g.N + bn - 1) / bn;
-  const long nt = (long)tm * tn * g.batch;
-  // split-K only for accumulating fp32 outputs with a linear epilogue (weight gradients): K is
-  // split over workgroups; partial sums go to fp32 slabs in the caller's scratch and are combined
-  // by splitk_reduce_kernel (HBM/MALL streaming, ~5 TB/s), or -- without scratch -- are added
-  // with fp32 atomics (~1.3 TB/s chip-wide, so only a fallback).
-  g.splitk = 1;
-  g.slab = nullptr;
-  if (can_split_ && nt < 256) {
-    int want = (int)((splitk_target + nt - 1) / nt);
-    int maxs = g.K / (4 * BK);
-    g.splitk = want < maxs ? want : maxs;
-    if (g.ws) {
-      long fit = g.ws_floats / ((long)g.M * g.N * g.batch);
-      if (fit < g.splitk) g.splitk = (int)fit;
-    }
-    if (g.splitk < 1) g.splitk = 1;
-  }
-  const int kt = (g.K + BK - 1) / BK;
-  g.kchunk = ((kt + g.splitk - 1) / g.splitk) * BK;
-  g.splitk = (g.K + g.kchunk - 1) / g.kchunk;
-  if (g.splitk < 1) g.splitk = 1;
-  g.tiles_n = tn;
-  const bool use_slab = g.splitk > 1 && g.ws != nullptr;
-  if (use_slab) g.slab = g.ws;
-  mark_fast_epilogue(g);
-  dim3 grid(tm * tn, g.batch * g.splitk, 1);
-  if (grid.y > 65535) return -2;
-  if (bm_out) *bm_out = bm * 1000 + bn;
-  // LDS-DMA ring kernel: aligned operands; rows-contiguous operands need a plain k stride
-  static const int use_dma = gemm_dma_enabled();
-  const bool dma_ok = vec && use_dma && dma_layout_ok(g);
-  // more tiles than CUs: the persistent kernel keeps the DMA ring running across the tiles a workgroup walks
-  // ... and, with a stream-K scratch bound to the stream, also the 128 x 128 launches that leave CUs idle (N = 512
-  // layers: 144 tiles) when K is long enough to share (launch_persistent decides)
-  bool sk_bound = false;
-  if (streamk_mode() > 0 && bm == 128 && bn == 128)
-    for (int i = 0; i < g_sk_n; ++i) sk_bound = sk_bound || (g_sk[i].st == st && g_sk[i].p);
-  if (dma_ok && g.batch == 1 && g.splitk == 1 && bm == 128 && persist_mode() > 0 && !w4bn &&
-      (persist_mode() == 2 || (persist_mode() == 3 && nt > num_cus()) || (sk_bound && (nt > num_cus() || (long)nt * ((g.K + BK - 1) / BK) >= 8L * num_cus())))) {
-    GemmGroup grp{};
-    int rc;
-    if (bn == 128) { add_to_group<128>(grp, g); rc = launch_persistent<128, 128, 4, 8>(grp, st); }
-    else { add_to_group<64>(grp, g); rc = launch_persistent<128, 64, 4, 8>(grp, st); }
-    if (rc) return rc;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  if (dma_ok) {
-    int rc;
-    // (one instantiation per tile shape: the interleaved steady state, 8 waves for 128-row tiles; the round-2 A/B forms
-    // -- plain loop, 4 waves, 2 / 3 / 5 ring stages, 64 x 128 -- were measured then and are no longer built)
-    if (p4 && g.splitk == 1) rc = s2st_gemm_bf16_p4(g, grid, st);
-    else if (w4bn && g.splitk == 1) rc = s2st_gemm_bf16_w4(g, bm, bn, grid, st);
-    else if (kExperimental && bm == 256 && bn == 128) { if constexpr (kExperimental) rc = launch_dma<256, 128, 3, 8>(g, grid, st); else rc = -1; }
-    else if (bm == 128 && bn == 128) rc = launch_dma<128, 128, 4, 8, true>(g, grid, st);
-    else if (bm == 128) rc = launch_dma<128, 64, 4, 8, true>(g, grid, st);
-    else if (bm == 160) rc = bn == 64 ? launch_dma<160, 64, 4, 8, true>(g, grid, st) : -1;
-    else rc = launch_dma<64, 64, 4, 4, true>(g, grid, st);
-    if (rc) return rc;
-  } else
-  if (bm == 160) return S2ST_ERR_ARG;  // (can160 implies the LDS-DMA kernels: never reached)
-  else if (!vec) launch_layouts<64, 64, false>(g, grid, st);
-  else if (bm == 128 && bn == 128) launch_layouts<128, 128, true>(g, grid, st);
-  else if (bm == 128) launch_layouts<128, 64, true>(g, grid, st);
-  else launch_layouts<64, 64, true>(g, grid, st);
-  if (use_slab) {
+  if (rc) return rc;
+  if (p.use_slab) {
     const long nthr = (long)g.M * ((g.N + 3) / 4);
     // bytes: every slab once, the result once (twice when it accumulates)
     const double by = 4.0 * g.M * g.N * g.batch * (g.splitk + 1 + (g.ep.accumulate ? 1 : 0));
@@ -1350,6 +1007,27 @@ int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* bm_out) {
                 dim3(256), 0, st, (const float*)g.slab, g.C, g.M, g.N, g.splitk, g.zdiv, g.ep.accumulate);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The plan of a product (n == 0) or a group, without launching; ncu / slots160 > 0 stand in for the device's (no HIP call)
+int s2st_gemm_bf16_plan(const GemmArgs* list, int n, int ncu, int slots160, bool sk_bound, s2st_gemm_plan_info* out) {
+  const GemmSwitches sw = gemm_switches(n ? SW_GROUP : SW_SINGLE);
+  const GemmChip chip = gemm_chip(sw, ncu, slots160);
+  GemmPlan p;
+  if (list[0].A.dtype != S2ST_BF16 || list[0].B.dtype != S2ST_BF16 || list[0].precise) p.error = S2ST_ERR_ARG;
+  else if (n == 0) p = plan_single(list[0], sw, chip, sk_bound);
+  else {
+    for (int i = 0; i < n && !p.error; ++i)
+      if (!group_member_ok(list[i], sw)) p.error = S2ST_ERR_SHAPE;
+    if (!p.error) p = plan_group(list, n, sw, chip, sk_bound);
+  }
+  *out = s2st_gemm_plan_info{p.error};
+  if (p.error) return 0;
+  *out = s2st_gemm_plan_info{0, (int)p.form, p.bm, p.bn, p.splitk, p.kchunk, p.tiles_n, p.use_slab, p.vec, p.cvec, p.grid_x, p.grid_y,
+                             p.sk, p.n, p.total};
+  for (int i = 0; i < p.n; ++i) out->cvec_of[i] = p.cvec_of[i];
+  gemm_tag(out->tag, sizeof out->tag, p.form, p.bm, p.bn, p.akm, p.bkm, p.form == GEMM_STAGED ? p.vec != 0 : p.sk);
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@
 // Replaces F.linear of fairseq/modules/transformer_layer.py:140-162, multihead_attention.py:170-192 and
 // fairseq/models/wav2vec/wav2vec2.py:736-814, 915-1016 (HuBERT projections / convolutions as GEMMs) in fast mode.
 #include "gemm_bf16_tile.h"
+#include "gemm_bf16_launch.h"
 
 namespace {
 
@@ -218,36 +219,16 @@ __global__ __launch_bounds__(64 * P4_NW) void gemm_bf16_p4_kernel(GemmArgs g) {
   gemm_p4_tile(g, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
 }
 
-double p4_flops(const GemmArgs& g) { return 2.0 * g.M * g.N * (double)g.K * g.batch; }
-double p4_min_bytes(const GemmArgs& g) {
-  const double mn = (double)g.M * g.N * g.batch;
-  return 2.0 * g.batch * ((double)g.M * g.K + (double)g.N * g.K) + mn * ((g.C.p ? 4 : 0) + (g.C.h ? 2 : 0)) +
-         mn * 4 * ((g.ep.accumulate ? 1 : 0) + (g.ep.resid ? 1 : 0));
-}
-
 }  // namespace
 
 // g: prepared by s2st_gemm_bf16 (alignment flags, tiles_n for the 256 x 256 tile, kchunk / splitk, epilogue marks);
 // both operands K-contiguous and 16-byte aligned (the caller checked)
 int s2st_gemm_bf16_p4(const GemmArgs& g, dim3 grid, hipStream_t st) {
   if (!g.A.kmajor || !g.B.kmajor) return S2ST_ERR_ARG;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_p4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            P4_LDS) != hipSuccess)
-      return -1;
-    configured = true;
-  }
-  s2st_launch("gemm_bf16_p4_kernel<256, 256>", p4_flops(g), p4_min_bytes(g), gemm_bf16_p4_kernel, grid, dim3(64 * P4_NW), P4_LDS,
-              st, g);
-  return 0;
+  return launch_configured<GEMM_P4, 256, 256, true, true, false>(gemm_bf16_p4_kernel, P4_LDS, grid, 64 * P4_NW, st, g);
 }
 
 int s2st_gemm_bf16_p4_preload(hipStream_t st) {
-  GemmArgs g{};
-  g.A.dtype = g.B.dtype = S2ST_BF16;
-  g.A.kmajor = g.B.kmajor = 1;
-  g.splitk = 1; g.zdiv = 1; g.tiles_n = 1; g.batch = 1; g.kchunk = BK;
-  const int rc = s2st_gemm_bf16_p4(g, dim3(1), st);
+  const int rc = s2st_gemm_bf16_p4(empty_problem(3), dim3(1), st);
   return rc || hipGetLastError() != hipSuccess ? -1 : 0;
 }

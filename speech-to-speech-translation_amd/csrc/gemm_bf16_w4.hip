@@ -19,6 +19,7 @@
 // (gemm_bf16_tile.h).  Replaces F.linear of fairseq/modules/transformer_layer.py:140-162 and
 // multihead_attention.py:170-192 (projections) in fast mode, like the kernels it sits beside.
 #include "gemm_bf16_tile.h"
+#include "gemm_bf16_launch.h"
 
 namespace {
 
@@ -147,63 +148,27 @@ __global__ __launch_bounds__(256, (w4_wgs_per_cu<BM, BN, NS>())) void gemm_bf16_
   gemm_w4_tile<BM, BN, AKM, BKM, NS>(grp.g[pi], t - grp.tile0[pi], grp.tile0[pi + 1] - grp.tile0[pi], 0);
 }
 
-double w4_flops(const GemmArgs& g) { return 2.0 * g.M * g.N * (double)g.K * g.batch; }
-double w4_min_bytes(const GemmArgs& g) {
-  const double mn = (double)g.M * g.N * g.batch;
-  return 2.0 * g.batch * ((double)g.M * g.K + (double)g.N * g.K) + mn * ((g.C.p ? 4 : 0) + (g.C.h ? 2 : 0)) +
-         mn * 4 * ((g.ep.accumulate ? 1 : 0) + (g.ep.resid ? 1 : 0));
-}
-
-template <int BM, int BN, int NS, bool GROUP, class ARG>
-int launch_w4(const ARG& arg, bool akm, bool bkm, dim3 grid, double fl, double by, hipStream_t st) {
-  constexpr int LDS = NS * (BM + BN) * 128;
-  static char tags[4][96];
-  auto go = [&](auto kern, int ti) {
-    static bool configured = false;  // one flag per instantiation (the lambda's operator() template)
-    if (!configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return -1;
-      configured = true;
-    }
-    if (!tags[ti][0])
-      snprintf(tags[ti], sizeof tags[ti], "gemm_bf16_w4%s_kernel<%d, %d, %s, %s, %d>", GROUP ? "_group" : "", BM, BN,
-               (ti & 2) ? "true" : "false", (ti & 1) ? "true" : "false", NS);
-    s2st_launch(tags[ti], fl, by, kern, grid, dim3(256), LDS, st, arg);
-    return 0;
-  };
-  if constexpr (GROUP) {
-    if (akm && bkm) return go(gemm_bf16_w4_group_kernel<BM, BN, true, true, NS>, 3);
-    if (akm && !bkm) return go(gemm_bf16_w4_group_kernel<BM, BN, true, false, NS>, 2);
-    if (!akm && bkm) return go(gemm_bf16_w4_group_kernel<BM, BN, false, true, NS>, 1);
-    return go(gemm_bf16_w4_group_kernel<BM, BN, false, false, NS>, 0);
-  } else {
-    if (akm && bkm) return go(gemm_bf16_w4_kernel<BM, BN, true, true, NS>, 3);
-    if (akm && !bkm) return go(gemm_bf16_w4_kernel<BM, BN, true, false, NS>, 2);
-    if constexpr (BM % 128 == 0) {  // (a 160-row A image exists K-contiguous only)
-      if (!akm && bkm) return go(gemm_bf16_w4_kernel<BM, BN, false, true, NS>, 1);
-      return go(gemm_bf16_w4_kernel<BM, BN, false, false, NS>, 0);
-    }
-    return -1;
-  }
+template <int BM, int BN, bool GROUP, class ARG>
+int launch_w4(const ARG& arg, dim3 grid, hipStream_t st) {
+  constexpr int LDS = W4_NS * (BM + BN) * 128;
+  return with_layouts<GROUP || BM % 128 == 0>(arg, [&](auto a, auto b) {  // (a 160-row A image exists K-contiguous only)
+    constexpr bool AKM = decltype(a)::value, BKM = decltype(b)::value;
+    if constexpr (GROUP)
+      return launch_configured<GEMM_GROUP_W4, BM, BN, AKM, BKM, false>(gemm_bf16_w4_group_kernel<BM, BN, AKM, BKM, W4_NS>, LDS, grid, 256, st, arg);
+    else
+      return launch_configured<GEMM_W4, BM, BN, AKM, BKM, false>(gemm_bf16_w4_kernel<BM, BN, AKM, BKM, W4_NS>, LDS, grid, 256, st, arg);
+  });
 }
 
 }  // namespace
 
 // g: prepared by s2st_gemm_bf16 (alignment flags, tiles_n for the chosen tile, kchunk / splitk, epilogue marks)
 int s2st_gemm_bf16_w4(const GemmArgs& g, int bm, int bn, dim3 grid, hipStream_t st) {
-  const bool akm = g.A.kmajor != 0, bkm = g.B.kmajor != 0;
-  const double fl = w4_flops(g), by = w4_min_bytes(g);
-  if (bm == 128 && bn == 128) return launch_w4<128, 128, 2, false>(g, akm, bkm, grid, fl, by, st);
-  if (bm == 128 && bn == 64) {
-    // two ring slots: 48 KB, three workgroups per CU (what w4_pick's slot count assumes; 4584 x 2048 x 512: 18.3 us against
-    // 22.0 us with three slots = two workgroups per CU, measured in round 3)
-    return launch_w4<128, 64, 2, false>(g, akm, bkm, grid, fl, by, st);
-  }
-  if (bm == 160 && bn == 128 && akm) {
-    // K-contiguous A only: wave tile 80 x 64, 2 x 36 KB of ring -- still two workgroups per CU (s2st_gemm_bf16_w4_slots
-    // asks the runtime), so M <= 5120 is 32 row tiles = one round where 128-row tiles need a second one
-    return launch_w4<160, 128, 2, false>(g, akm, bkm, grid, fl, by, st);
-  }
+  if (bm == 128 && bn == 128) return launch_w4<128, 128, false>(g, grid, st);
+  if (bm == 128 && bn == 64) return launch_w4<128, 64, false>(g, grid, st);
+  // K-contiguous A only: wave tile 80 x 64, 2 x 36 KB of ring -- still two workgroups per CU (s2st_gemm_bf16_w4_slots
+  // asks the runtime), so M <= 5120 is 32 row tiles = one round where 128-row tiles need a second one
+  if (bm == 160 && bn == 128 && g.A.kmajor) return launch_w4<160, 128, false>(g, grid, st);
   return S2ST_ERR_ARG;
 }
 
@@ -225,24 +190,18 @@ int s2st_gemm_bf16_w4_slots160() {
 }
 
 int s2st_gemm_bf16_w4_group(const GemmGroup& grp, hipStream_t st) {
-  double fl = 0, by = 0;
-  for (int i = 0; i < grp.n; ++i) { fl += w4_flops(grp.g[i]); by += w4_min_bytes(grp.g[i]); }
-  const bool akm = grp.g[0].A.kmajor != 0, bkm = grp.g[0].B.kmajor != 0;
-  return launch_w4<128, 128, 2, true>(grp, akm, bkm, dim3(grp.total < 1 ? 1 : grp.total), fl, by, st);
+  return launch_w4<128, 128, true>(grp, dim3(grp.total < 1 ? 1 : grp.total), st);
 }
 
 int s2st_gemm_bf16_w4_preload(hipStream_t st) {
-  GemmArgs g{};
-  g.A.dtype = g.B.dtype = S2ST_BF16;
-  g.splitk = 1; g.zdiv = 1; g.tiles_n = 1; g.batch = 1; g.kchunk = BK;
   int rc = 0;
   for (int lay = 0; lay < 4; ++lay) {
-    g.A.kmajor = lay & 1; g.B.kmajor = (lay >> 1) & 1;
-    rc |= s2st_gemm_bf16_w4(g, 128, 128, dim3(1), st);
-    rc |= launch_w4<128, 64, 2, false>(g, g.A.kmajor != 0, g.B.kmajor != 0, dim3(1), 0.0, 0.0, st);
-    if (g.A.kmajor) rc |= launch_w4<160, 128, 2, false>(g, true, g.B.kmajor != 0, dim3(1), 0.0, 0.0, st);
     GemmGroup grp{};
-    grp.n = 1; grp.g[0] = g; grp.total = 0;
+    grp.n = 1;
+    const GemmArgs& g = grp.g[0] = empty_problem(lay);
+    rc |= s2st_gemm_bf16_w4(g, 128, 128, dim3(1), st);
+    rc |= s2st_gemm_bf16_w4(g, 128, 64, dim3(1), st);
+    if (g.A.kmajor) rc |= s2st_gemm_bf16_w4(g, 160, 128, dim3(1), st);
     rc |= s2st_gemm_bf16_w4_group(grp, st);
   }
   return rc || hipGetLastError() != hipSuccess ? -1 : 0;

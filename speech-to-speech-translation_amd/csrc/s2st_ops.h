@@ -12,16 +12,15 @@ static inline bool s2st_env_on(const char* name) { return s2st_env_int(name, 0) 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "s2st_common.h"
+#include "gemm_bf16_plan.h"  // the bf16 dispatcher's decisions (host-only); S2ST_GROUP_MAX, S2ST_STREAMK_*
 
 // ---------------------------------------------------------------------------------------
 // GEMM:  C(m, n) = epilogue( alpha * sum_k A(m, k) * B(n, k) )      fp32 in HBM,
 // bf16 MFMA (v_mfma_f32_16x16x32_bf16) with fp32 accumulation; `precise` selects the
 // bf16x3 split (a_hi*b_hi + a_hi*b_lo + a_lo*b_hi, ~fp32 accuracy) used by parity tests.
 // ---------------------------------------------------------------------------------------
-typedef s2st_gemm_operand GemmOperand;
 typedef s2st_gemm_out GemmOut;
 typedef s2st_gemm_epilogue GemmEpilogue;
-typedef s2st_gemm_args GemmArgs;
 
 inline GemmOperand gemm_rowmajor(const float* p, long ld) {  // X[r][k], k contiguous
   GemmOperand o;
@@ -60,7 +59,6 @@ inline GemmEpilogue gemm_epi_default() {
 
 // up to S2ST_GROUP_MAX bf16 problems with the same operand layouts in ONE persistent launch (gemm_bf16.hip): batch 1,
 // no split-K; total = tile0[n] tiles of the launcher's tile size
-#define S2ST_GROUP_MAX 8
 struct GemmGroup {
   int n, total;
   int tile0[S2ST_GROUP_MAX + 1];
@@ -77,8 +75,6 @@ struct GemmGroup {
 };
 // scratch for stream-K launches on `st` (nullptr: none -- the launcher then keeps whole tiles per workgroup);
 // floats >= S2ST_STREAMK_SCRATCH_FLOATS; the first 16 ints must be zero at bind time
-#define S2ST_STREAMK_MAX_WGS 512
-#define S2ST_STREAMK_SCRATCH_FLOATS (1024 + (long)S2ST_STREAMK_MAX_WGS * 128 * 128)
 void s2st_gemm_streamk_bind(hipStream_t st, float* scratch, long floats);
 void s2st_gemm_streamk_unbind_all();
 // true if g can join a group (aligned bf16 operands, plain strides, batch 1, >= 128 x 128 of output)
@@ -86,6 +82,8 @@ bool s2st_gemm_group_ok(const GemmArgs& g);
 int s2st_gemm_bf16_group(const GemmArgs* list, int n, hipStream_t st);
 int s2st_gemm(GemmArgs g, hipStream_t st, int* tile_out = nullptr /* bf16 path: tile rows * 1000 + tile columns */);
 int s2st_gemm_bf16(GemmArgs g, hipStream_t st, int* tile_out);
+// what s2st_gemm_bf16 (n == 0: list[0]) / s2st_gemm_bf16_group (n problems) would launch; ncu, slots160 <= 0: this device's
+int s2st_gemm_bf16_plan(const GemmArgs* list, int n, int ncu, int slots160, bool sk_bound, s2st_gemm_plan_info* out);
 // skinny-M (<= 16 rows) y = f(x W^T + b) (+ resid) with fp32 x converted in registers (AR decoding)
 int s2st_gemm_skinny(const float* A, long lda, const bf16raw* W, long ldw, float* C, long ldc, const float* bias, int act,
                      float drop_p, uint64_t seed, const float* resid, long ldr, int M, int N, int K, hipStream_t st,
@@ -100,7 +98,7 @@ int s2st_gemm_bf16_w4(const GemmArgs& g, int bm, int bn, dim3 grid, hipStream_t 
 int s2st_gemm_bf16_w4_slots160();  // workgroups of the 160 x 128 form per CU, from the runtime's occupancy query
 int s2st_gemm_bf16_w4_group(const GemmGroup& grp, hipStream_t st);
 int s2st_gemm_bf16_w4_preload(hipStream_t st);
-// 256 x 256 four-phase form (gemm_bf16_p4.hip): both operands K-contiguous, chosen by p4_pick() in gemm_bf16.hip
+// 256 x 256 four-phase form (gemm_bf16_p4.hip): both operands K-contiguous, chosen by p4_pick() in gemm_bf16_plan.h
 int s2st_gemm_bf16_p4(const GemmArgs& g, dim3 grid, hipStream_t st);
 int s2st_gemm_bf16_p4_preload(hipStream_t st);
 int s2st_gemm_bf16_preload(hipStream_t st);  // load every instantiation (empty launches)  // gemm_bf16.hip (both operands bf16)

@@ -8,6 +8,7 @@ never does that.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Optional
@@ -177,6 +178,35 @@ def gemm_group(problems):
     """s2st_gemm_group_f32: up to 8 bf16 problems of the same operand layouts in one persistent launch."""
     arr = (GemmArgs * len(problems))(*problems)
     check(lib().s2st_gemm_group_f32(arr, len(problems), C.c_void_p(stream_ptr())), "s2st_gemm_group_f32")
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("error", "form", "bm", "bn", "splitk", "kchunk", "tiles_n", "use_slab", "vec", "cvec",
+                                         "grid_x", "grid_y", "sk", "n", "total")] + \
+               [("cvec_of", C.c_int32 * 8), ("tag", C.c_char * 104)]
+
+
+GEMM_FORMS = ("STAGED", "RING", "W4", "P4", "PERSISTENT", "RING_256x128", "GROUP_RING", "GROUP_W4", "GROUP_PERSISTENT",
+              "GROUP_PERSISTENT_256")
+GemmPlan = collections.namedtuple("GemmPlan", "error form tag bm bn splitk kchunk tiles_n use_slab vec cvec grid sk n total cvec_of")
+
+
+def gemm_plan(args, ncu=0, slots160=0, sk_bound=False, _info=GemmPlanInfo()) -> GemmPlan:
+    """What ``gemm`` (one GemmArgs, e.g. from ``gemm_args_bf16``) or ``gemm_group`` (a list of them) would launch under the
+    switches now in the environment, without launching: s2st_gemm_plan_f32.  ``ncu`` / ``slots160`` > 0 stand in for the
+    device's CU count and its workgroups of the 160 x 128 4-wave form per CU (no HIP call then: a 256-CU decision can be
+    asked on any host); ``error`` is the code the launch would fail with (the other fields are then None / zero)."""
+    p = _info
+    if isinstance(args, GemmArgs):
+        rc = lib().s2st_gemm_plan_f32(C.byref(args), ncu, slots160, 1 if sk_bound else 0, C.byref(p))
+    else:
+        arr = (GemmArgs * len(args))(*args)
+        rc = lib().s2st_gemm_group_plan_f32(arr, len(args), ncu, slots160, 1 if sk_bound else 0, C.byref(p))
+    check(rc, "s2st_gemm_plan_f32")
+    if p.error:
+        return GemmPlan(p.error, None, None, 0, 0, 0, 0, 0, False, False, 0, (0, 0), False, 0, 0, ())
+    return GemmPlan(0, GEMM_FORMS[p.form], p.tag.decode(), p.bm, p.bn, p.splitk, p.kchunk, p.tiles_n, bool(p.use_slab), bool(p.vec),
+                    p.cvec, (p.grid_x, p.grid_y), bool(p.sk), p.n, p.total, tuple(p.cvec_of[:p.n]))
 
 
 class AttnArgs(C.Structure):

@@ -5,6 +5,8 @@ Per output element the K order and the MFMA shape are those of the 128-row tiles
 element, so the criterion is not a tolerance: C (fp32 and bf16) of a launch forced to a 160-row tile equals the same
 call forced to the 128-row tile of the same width bit for bit.  Only the column sums of the masked epilogue regroup
 (wave rows of 80 instead of 64 rows); their bound is derived in _colsum_bound()."""
+import ctypes
+
 import pytest
 import torch
 
@@ -145,9 +147,15 @@ def test_unforced_pick_at_the_step_shapes(monkeypatch):
         A = torch.randn(M, K, generator=g).to(torch.bfloat16).to(d)
         B = (torch.randn(N, K, generator=g) / K ** 0.5).to(torch.bfloat16).to(d)
         C = torch.zeros(M, N, device=d)
+        plan = bd.gemm_plan(bd.gemm_args_bf16(A, B, C, M, N, K))  # (ncu = 0: this chip's) the query names the same launch
+        bd.lib().s2st_profile_enable(1)
         t = bd.gemm(A, B, C, M, N, K, return_tile=True)
         torch.cuda.synchronize()
+        bd.lib().s2st_profile_enable(0)
         assert t == want, ((M, N, K), t)
+        buf = ctypes.create_string_buffer(1 << 16)
+        n = bd.lib().s2st_profile_report(buf, len(buf))
+        assert (plan.bm, plan.bn) == want and [ln.split("\t")[0] for ln in buf.raw[:max(n, 0)].decode().splitlines()] == [plan.tag], plan
         monkeypatch.setenv("S2ST_GEMM_TILE", "128x128")
         C2 = torch.zeros(M, N, device=d)
         bd.gemm(A, B, C2, M, N, K)
