@@ -139,9 +139,8 @@ struct s2st_engine {
     // No stream priorities: a plain second stream carries the same schedule.  This is also what gives the CPU emulator
     // (tests/hipemu: its priority form always fails) a second stream at all -- a label there, every launch is synchronous --
     // so the emulator suite now walks the second-stream schedule (aux heads, hoisted K|V projections, weight-gradient forks,
-    // S2ST_DEC_OVERLAP) in its issue order instead of the one-stream one.  Not next to the two-chain mode's own stream: the
-    // emulator hands out ONE stream handle, and a second stream equal to chain1_ would be taken for it (ws_for, chain_count).
-    if (!side_ && !chain1_ && hipStreamCreateWithFlags(&side_, hipStreamNonBlocking) != hipSuccess) side_ = nullptr;
+    // S2ST_DEC_OVERLAP) in its issue order instead of the one-stream one.
+    if (!side_ && hipStreamCreateWithFlags(&side_, hipStreamNonBlocking) != hipSuccess) side_ = nullptr;
     bool ev_ok = side_ != nullptr;
     if (side_ && hipEventCreateWithFlags(&ev_kv_, hipEventDisableTiming) != hipSuccess) { ev_kv_ = nullptr; ev_ok = false; }
     if (side_ && hipEventCreateWithFlags(&ev_head_, hipEventDisableTiming) != hipSuccess) { ev_head_ = nullptr; ev_ok = false; }
@@ -155,13 +154,9 @@ struct s2st_engine {
     side_events_ = side_ && ev_ok;
   }
   hipStream_t fork_side() {  // everything issued on st_ so far happens-before what follows on the returned stream
-    if (!side_) { sync_chains(); return st_; }
+    if (!side_) return st_;
     hipEventRecord(ev_fork_, st_);
     hipStreamWaitEvent(side_, ev_fork_, 0);
-    if (forked_) {  // ... and everything issued on the second chain
-      hipEventRecord(ev_cside_, chain1_);
-      hipStreamWaitEvent(side_, ev_cside_, 0);
-    }
     side_used = true;
     return side_;
   }
@@ -181,69 +176,12 @@ struct s2st_engine {
     stalls.push_back(s);
   }
   void join_side() {
-    sync_chains();
     if (!side_ || !side_used) return;
     hipEventRecord(ev_join_, side_);
     wait_traced(st_, ev_join_, "join_side");
     side_used = false;
   }
 
-  // ---- two utterance-half chains (round 5; S2ST_CHAINS=2) -----------------------------------------
-  // Between the conv front end and the post-net every op of the training step is independent across utterances: rows of
-  // the linear layers and layer norms, attention per (utterance, head).  In this mode those ops are launched TWICE -- rows
-  // of utterances [0, B/2) on the caller's stream, rows of [B/2, B) on a second chain stream -- over the SAME whole-batch
-  // tensors, so that one chain's per-kernel latency (launch boundary, prologue, a single round of tiles) runs under the
-  // other's.  Everything that spans the batch stays ONE launch behind both chains: the weight-gradient products (K = all
-  // tokens: fork_side waits for both), BatchNorm / convolutions / losses (sync_chains in front of them), the partial-sum
-  // folds (both chains' partial rows, chain 0's first).  Dropout masks are keyed by (seed, element index of the LAUNCH):
-  // chain 1 salts its seed, so its masks are independent of chain 0's (they differ from the one-chain schedule's masks for
-  // those rows -- same distribution; with dropout off the two schedules' forward outputs are bit-identical).
-  int nchains = 1;               // S2ST_CHAINS
-  hipStream_t chain1_ = nullptr;
-  hipEvent_t ev_cfork_ = nullptr, ev_cjoin_ = nullptr, ev_cside_ = nullptr;
-  bool forked_ = false;
-  bool in_region_ = false;       // forward: between chain_region(true) and chain_region(false); backward: per closure
-  hipStream_t main_ = nullptr;   // the caller's stream of this call (st_ points at side_ while the aux sections run)
-  float* skws_c1 = nullptr;      // split-K scratch of the second chain
-  std::vector<char> tape_aware;  // closure i launches per chain itself (everything else gets sync_chains() first)
-  static constexpr uint64_t CHAIN_SALT = 0xD6E8FEB86659FD93ULL;
-  struct Part { int r0, nr; hipStream_t st; uint64_t salt; };
-  // how many parts an op over `rows` rows (rows = B x positions) is launched in -- independent of live(), so that the dry
-  // run of the schedule allocates what the real one does
-  int chain_count(int rows) const {
-    return (nchains == 2 && chain1_ && in_region_ && st_ == main_ && bt.B >= 2 && rows > 0 && rows % bt.B == 0) ? 2 : 1;
-  }
-  int chain_parts(int rows, Part* p) {
-    if (chain_count(rows) == 1) {
-      if (live()) sync_chains();
-      p[0] = Part{0, rows, st_, 0};
-      return 1;
-    }
-    const int per = rows / bt.B, b0 = bt.B / 2;
-    if (live()) ensure_forked();
-    p[0] = Part{0, b0 * per, main_, 0};
-    p[1] = Part{b0 * per, rows - b0 * per, chain1_, CHAIN_SALT};
-    return 2;
-  }
-  void ensure_forked() {
-    if (forked_) return;
-    hipEventRecord(ev_cfork_, main_);
-    hipStreamWaitEvent(chain1_, ev_cfork_, 0);
-    forked_ = true;
-  }
-  void sync_chains() {  // the caller's stream takes in what the second chain did
-    if (!forked_) return;
-    hipEventRecord(ev_cjoin_, chain1_);
-    hipStreamWaitEvent(main_, ev_cjoin_, 0);
-    forked_ = false;
-  }
-  void set_aware() {
-    tape_aware.resize(tape.size(), 0);
-    if (!tape.empty()) tape_aware.back() = in_region_ ? 1 : 0;
-  }
-  void chains_wait(hipEvent_t ev) {  // an event both chains have to honour (work handed over from the second stream)
-    if (forked_) hipStreamWaitEvent(chain1_, ev, 0);
-  }
   // ---- AR decoding state (config 5): caller-owned cache buffer laid out by decode_begin --------
   // replay_ != null: decode_step in its graph-replayable form (s2st_engine_decode_step_replay): the step, the prenet's dropout
   // seeds, the input frame, the position row and the output rows are read from / written to the fixed device buffers of *replay_
@@ -261,8 +199,6 @@ struct s2st_engine {
   float* dec_crossKV(int l) const {
     return dec_st.base + (long)c.dec_layers * 2 * dec_st.B * dec_st.maxT * c.dec_dim + (long)l * dec_st.B * dec_st.E * 2 * c.dec_dim;
   }
-                             // (0 = none).  Balances the two streams; measured on the bench workload: n = 3 .. 16,
-                             // best 7 (11.15 -> 10.89 ms/step together with the attention-backward bf16 gradients)
   bool use_ln_skinny = true; // S2ST_NO_LN_SKINNY=1 (A/B switch): separate layer-norm kernels in the AR decoding steps
   bool use_skinny = true;    // S2ST_NO_SKINNY=1 (A/B switch): tiled GEMMs for the AR decoding steps too
   bool use_ln_fuse = true;  // S2ST_NO_LN_FUSE=1 (A/B switch): separate dropout-backward prologue pass
@@ -283,9 +219,6 @@ struct s2st_engine {
   // option at +3 % of a step (one small fold launch per sum); the folds now ride in the segment's batched fold launch
   // (pending_lnfold), i.e. cost no launches of their own.
   bool ordered_sums = true;
-                               // Emitting the bf16 GEMM operands from the attention backward takes 0.6 ms off the
-                               // data-path stream but makes the second stream the longer one (its final join grew from
-                               // 0.1 to 0.6 ms): it only pays together with wgrad_main_every below
   bool use_act_fuse = true;  // S2ST_NO_ACT_FUSE=1: separate ReLU-dropout backward kernel (A/B switch)
   bool use_flash = true;  // S2ST_NO_FLASH=1: unfused attention everywhere (A/B switch)
   // S2ST_ATTN_KEEP_F32=1 (A/B switch): the fused attention also stores O in fp32 and the out-projection's data-gradient
@@ -301,7 +234,7 @@ struct s2st_engine {
   struct HubP {
     long conv_w[8]; long gn_g, gn_b; LNP ln; LinP proj; long pos_w, pos_b; std::vector<EncLayerP> L; LNP enc_ln;
   } hp;
-  float* ws_for(hipStream_t s) const { return (side_ && s == side_) ? skws_side : ((chain1_ && s == chain1_) ? skws_c1 : skws); }
+  float* ws_for(hipStream_t s) const { return (side_ && s == side_) ? skws_side : skws; }
   float* skws = nullptr;  // split-K partial-sum scratch of the weight-gradient GEMMs (per call)
   long skws_n = 0;
   bool ph_fresh = false;   // s2st_engine_bf16_is_fresh: PH already equals bf16(P) for the next forward
@@ -435,6 +368,8 @@ int s2st_engine_create(const s2st_model_config* cfg, s2st_engine** out) {
                         cfg->conv_channels % 16 || (cfg->has_asr && cfg->asr_dim % 8) ||
                         (cfg->has_st && cfg->st_dim % 8)))
     return S2ST_ERR_SHAPE;
+  // the two-utterance-half-chain schedule measured neutral and was removed (profiles/r05_chains_ab.txt): asked for and not available is loud
+  if (!cfg->precise && s2st_env_int("S2ST_CHAINS", 1) != 1) return S2ST_ERR_ARG;
   s2st_engine* e = new s2st_engine();
   e->c = *cfg;
   e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
@@ -466,15 +401,6 @@ int s2st_engine_create(const s2st_model_config* cfg, s2st_engine** out) {
   // then shares a queue with one of the generator's chains (config 5, profiles/r05_queue_matrix.txt).
   e->side_allowed = !cfg->precise && !(s2st_env_on("S2ST_NO_SIDE_STREAM"));
   e->overlap_aux = !(s2st_env_on("S2ST_NO_AUX_OVERLAP"));
-  // S2ST_CHAINS=2: the training step's layers as two utterance-half chains (see chain_count)
-  if (!cfg->precise && s2st_env_int("S2ST_CHAINS", 1) == 2) {
-    if (hipStreamCreateWithFlags(&e->chain1_, hipStreamNonBlocking) == hipSuccess &&
-        hipEventCreateWithFlags(&e->ev_cfork_, hipEventDisableTiming) == hipSuccess &&
-        hipEventCreateWithFlags(&e->ev_cjoin_, hipEventDisableTiming) == hipSuccess &&
-        hipEventCreateWithFlags(&e->ev_cside_, hipEventDisableTiming) == hipSuccess)
-      e->nchains = 2;
-    else { delete e; return S2ST_ERR_LAUNCH; }  // (asked for and not available: loud)
-  }
   *out = e;
   return 0;
 }
@@ -491,13 +417,6 @@ void s2st_engine_destroy(s2st_engine* e) {
     if (e->ev_kv_) hipEventDestroy(e->ev_kv_);
     if (e->ev_head_) hipEventDestroy(e->ev_head_);
     for (hipEvent_t ev : e->adam_ev) hipEventDestroy(ev);
-  }
-  if (e->chain1_) {
-    hipStreamSynchronize(e->chain1_);
-    hipStreamDestroy(e->chain1_);
-    if (e->ev_cfork_) hipEventDestroy(e->ev_cfork_);
-    if (e->ev_cjoin_) hipEventDestroy(e->ev_cjoin_);
-    if (e->ev_cside_) hipEventDestroy(e->ev_cside_);
   }
   e->reset_call();
   delete e;

@@ -40,40 +40,27 @@
     if (fm && act == 0 && drop_p > 0.f && N % 8 == 0 && use_ln_fuse) {
       y->drop2_ok = true; y->drop2_p = drop_p; y->drop2_seed = sd; y->drop2_bias = b;
     }
-    Part pt[2];
-    const int np = chain_parts(M, pt);  // (two utterance-half chains: rows [r0, r0 + nr) on each chain's stream)
     if (live()) {
-      for (int ci = 0; ci < np; ++ci) {
-        const long r0 = pt[ci].r0;
-        GemmArgs g{};
-        g.A = fm ? gemm_rowmajor(xh + r0 * x->hld(), x->hld()) : gemm_rowmajor(x->d + r0 * x->cols, x->cols);
-        g.B = fm ? gemm_rowmajor(PH + w, K) : gemm_rowmajor(P + w, K);
-        g.C = gemm_out(y->d ? y->d + r0 * N : nullptr, N);
-        g.C.h = y->h ? y->h + r0 * N : nullptr;
-        g.ep = gemm_epi_default();
-        g.ep.bias = b >= 0 ? P + b : nullptr;
-        g.ep.act = act;
-        g.ep.drop_p = drop_p;
-        g.ep.seed = sd ^ pt[ci].salt;
-        g.ep.resid = resid ? resid->d + r0 * N : nullptr;
-        g.M = pt[ci].nr; g.N = N; g.K = K; g.batch = 1; g.zdiv = 1; g.precise = c.precise;
-        chk(s2st_gemm(g, pt[ci].st));
-      }
+      GemmArgs g{};
+      g.A = fm ? gemm_rowmajor(xh, x->hld()) : gemm_rowmajor(x->d, x->cols);
+      g.B = fm ? gemm_rowmajor(PH + w, K) : gemm_rowmajor(P + w, K);
+      g.C = gemm_out(y->d, N);
+      g.C.h = y->h;
+      g.ep = gemm_epi_default();
+      g.ep.bias = b >= 0 ? P + b : nullptr;
+      g.ep.act = act;
+      g.ep.drop_p = drop_p;
+      g.ep.seed = sd;
+      g.ep.resid = resid ? resid->d : nullptr;
+      g.M = M; g.N = N; g.K = K; g.batch = 1; g.zdiv = 1; g.precise = c.precise;
+      chk(s2st_gemm(g, st_));
     }
-    const bool region = in_region_;
     tape.push_back([=]() {
-      const bool region_was = in_region_;
-      in_region_ = region;
-      struct Restore { bool& r; bool v; ~Restore() { r = v; } } restore_{in_region_, region_was};
-      Part bp[2];
-      const int nb = chain_parts(M, bp);
       if (!y->g && !y->gpre_h) return;  // nothing flowed back
       float* dy = y->g;
       if (resid && resid->needs_grad) {
         if (!resid->g) resid->g = dy;  // alias: every reader of dy runs before resid's producers
-        else if (live())
-          for (int ci = 0; ci < nb; ++ci)
-            chk(s2st_axpy(dy + (long)bp[ci].r0 * N, resid->g + (long)bp[ci].r0 * N, (long)bp[ci].nr * N, 1.f, bp[ci].st));
+        else if (live()) chk(s2st_axpy(dy, resid->g, (long)M * N, 1.f, st_));
       }
       float* dpre = dy;
       const int ldp = (N + 7) & ~7;
@@ -88,23 +75,16 @@
         const int mode = act == 1 ? 1 : (drop_p > 0.f ? 2 : 0);
         // (bias sums in a fixed order: a bias whose gradient is mathematically zero -- key projections -- gets pure rounding
         // noise, which must repeat from run to run)
-        float* part[2] = {nullptr, nullptr};
-        for (int ci = 0; ci < nb; ++ci)
-          part[ci] = (b >= 0 && ordered_sums) ? alloc(s2st_linear_bwd_prep_scratch_floats(M, N, ldp)) : nullptr;
+        float* part = (b >= 0 && ordered_sums) ? alloc(s2st_linear_bwd_prep_scratch_floats(M, N, ldp)) : nullptr;
         if (live()) {
-          for (int ci = 0; ci < nb; ++ci) {
-            const long r0 = bp[ci].r0;
-            int slabs = 0;
-            chk(s2st_linear_bwd_prep(dy + r0 * N, y->d ? y->d + r0 * N : nullptr, y->d ? nullptr : y->h + r0 * N, mode, drop_p,
-                                     sd ^ bp[ci].salt, t + r0 * ldp, ldp, nullptr, b >= 0 ? G + b : nullptr, bp[ci].nr, N, bp[ci].st,
-                                     part[ci], part[ci] ? &slabs : nullptr));
-            if (part[ci]) add_fold(part[ci], slabs, N, G + b);
-          }
+          int slabs = 0;
+          chk(s2st_linear_bwd_prep(dy, y->d, y->d ? nullptr : y->h, mode, drop_p, sd, t, ldp, nullptr, b >= 0 ? G + b : nullptr, M, N,
+                                   st_, part, part ? &slabs : nullptr));
+          if (part) add_fold(part, slabs, N, G + b);
         }
         dph = t;
         bias_done = true;
       } else {
-        if (live()) sync_chains();  // (whole-tensor passes of the precise / odd-width path)
         if (act == 1) {
           dpre = alloc(y->n());
           if (live()) chk(s2st_relu_drop_bwd(dy, y->d, dpre, y->n(), drop_p, st_));
@@ -135,7 +115,6 @@
           // (no slabs, no combine kernels): see flush_wgrad()
           push_wgrad(g);
         } else {
-          if (!(fm && !on_main)) sync_chains();  // (a whole-batch product on the data-path stream)
           hipStream_t ws_st = fm && !on_main ? fork_side() : st_;
           g.ws = ws_for(ws_st); g.ws_floats = skws_n;
           chk(s2st_gemm(g, ws_st));
@@ -152,45 +131,39 @@
         if (fm && !acc && x->want_gh && x->hld() == x->cols) x->gh = alloc_h(x->n());
         const bool fuse_act = fm && !acc && x->act_mode == 1 && x->h && x->hld() == x->cols && use_act_fuse;
         if (fuse_act) x->gpre_h = alloc_h(x->n());
-        float* cs_part[2] = {nullptr, nullptr};
-        for (int ci = 0; ci < nb; ++ci)
-          cs_part[ci] = (fuse_act && ordered_sums && x->act_bias >= 0) ? alloc((long)2 * ((M + 63) / 64) * K) : nullptr;
+        float* cs_part = (fuse_act && ordered_sums && x->act_bias >= 0) ? alloc((long)2 * ((M + 63) / 64) * K) : nullptr;
         if (live()) {
-          if (nb == 2) ensure_forked();  // (a whole-batch pass above may have joined the chains)
-          for (int ci = 0; ci < nb; ++ci) {
-            const long r0 = bp[ci].r0;
-            GemmArgs g{};  // dx[M][K] (+)= dpre W
-            g.A = fm ? gemm_rowmajor(dph + r0 * ldp, ldp) : gemm_rowmajor(dpre + r0 * N, N);
-            g.B = fm ? (has_wt(w, N, K) ? gemm_rowmajor(PHT + w, N) : gemm_colmajor(PH + w, K)) : gemm_colmajor(P + w, K);
-            g.C = gemm_out(dx + r0 * x->cols, x->cols);
-            if (fm && !acc && x->gh) g.C.h = x->gh + r0 * x->cols;  // the consumer (attention backward) reads dO as a GEMM operand
-            if (fm && !acc && x->gh && x->gh_only) g.C.p = nullptr;  // ... and nothing reads the fp32 form (dx stays allocated: the consumer's closure tests it)
-            g.ep = gemm_epi_default();
-            if (fuse_act) {  // dx is the gradient w.r.t. a ReLU+dropout output: emit its pre-activation gradient
-              g.C.p = nullptr;
-              g.C.h = x->gpre_h + r0 * x->cols;
-              g.ep.mask_y = x->h + r0 * x->cols;
-              g.ep.mask_scale = x->act_p > 0.f ? 1.f / (1.f - x->act_p) : 1.f;
-              g.ep.colsum = x->act_bias >= 0 ? G + x->act_bias : nullptr;
-            }
-            g.ep.accumulate = acc ? 1 : 0;
-            g.ws = ws_for(bp[ci].st); g.ws_floats = skws_n;
-            g.M = bp[ci].nr; g.N = K; g.K = N; g.batch = 1; g.zdiv = 1; g.precise = c.precise;
-            if (fuse_act && g.ep.colsum && ordered_sums) {
-              // the bias gradient of the masked layer as per-(row tile, wave row) partial rows (worst case: 64-row tiles)
-              g.ep.colsum_part = cs_part[ci];
-              int tile = 0;
-              chk(s2st_gemm(g, bp[ci].st, &tile));
-              const int bm = tile / 1000;
-              if (bm > 0) add_fold(cs_part[ci], 2 * ((bp[ci].nr + bm - 1) / bm), K, g.ep.colsum);
-              else if (!err) err = S2ST_ERR_LAUNCH;
-            } else
-            chk(s2st_gemm(g, bp[ci].st));
+          GemmArgs g{};  // dx[M][K] (+)= dpre W
+          g.A = fm ? gemm_rowmajor(dph, ldp) : gemm_rowmajor(dpre, N);
+          g.B = fm ? (has_wt(w, N, K) ? gemm_rowmajor(PHT + w, N) : gemm_colmajor(PH + w, K)) : gemm_colmajor(P + w, K);
+          g.C = gemm_out(dx, x->cols);
+          if (fm && !acc && x->gh) g.C.h = x->gh;  // the consumer (attention backward) reads dO as a GEMM operand
+          if (fm && !acc && x->gh && x->gh_only) g.C.p = nullptr;  // ... and nothing reads the fp32 form (dx stays allocated: the consumer's closure tests it)
+          g.ep = gemm_epi_default();
+          if (fuse_act) {  // dx is the gradient w.r.t. a ReLU+dropout output: emit its pre-activation gradient
+            g.C.p = nullptr;
+            g.C.h = x->gpre_h;
+            g.ep.mask_y = x->h;
+            g.ep.mask_scale = x->act_p > 0.f ? 1.f / (1.f - x->act_p) : 1.f;
+            g.ep.colsum = x->act_bias >= 0 ? G + x->act_bias : nullptr;
+          }
+          g.ep.accumulate = acc ? 1 : 0;
+          g.ws = ws_for(st_); g.ws_floats = skws_n;
+          g.M = M; g.N = K; g.K = N; g.batch = 1; g.zdiv = 1; g.precise = c.precise;
+          if (fuse_act && g.ep.colsum && ordered_sums) {
+            // the bias gradient of the masked layer as per-(row tile, wave row) partial rows (worst case: 64-row tiles)
+            g.ep.colsum_part = cs_part;
+            int tile = 0;
+            chk(s2st_gemm(g, st_, &tile));
+            const int bm = tile / 1000;
+            if (bm > 0) add_fold(cs_part, 2 * ((M + bm - 1) / bm), K, g.ep.colsum);
+            else if (!err) err = S2ST_ERR_LAUNCH;
+          } else {
+            chk(s2st_gemm(g, st_));
           }
         }
       }
     });
-    set_aware();
     return y;
   }
 
@@ -217,64 +190,39 @@
     float* rstd = alloc(x->rows);
     touch(p.b + p.C);
     if (fast() && x->cols % 8 == 0) y->h = alloc_h(y->n());
-    Part pt[2];
-    const int np = chain_parts(x->rows, pt);
-    if (live())
-      for (int ci = 0; ci < np; ++ci) {
-        const long r0 = pt[ci].r0, o = r0 * x->cols;
-        chk(s2st_layernorm_fwd(x->d + o, P + p.g, P + p.b, y->d ? y->d + o : nullptr, mean + r0, rstd + r0, pt[ci].nr, x->cols, 1e-5f,
-                               pt[ci].st, y->h ? y->h + o : nullptr));
-      }
+    if (live()) chk(s2st_layernorm_fwd(x->d, P + p.g, P + p.b, y->d, mean, rstd, x->rows, x->cols, 1e-5f, st_, y->h));
     LNP pp = p;
-    const bool region = in_region_;
     // first layer norm applied to x (forward order): its backward is the last contribution to x's gradient
     const bool fuse_cand = fast() && x->drop2_ok && !x->ln_seen && x->needs_grad;
     x->ln_seen = true;
     tape.push_back([=]() {
       if (!y->g) return;
-      const bool region_was = in_region_;
-      in_region_ = region;
-      struct Restore { bool& r; bool v; ~Restore() { r = v; } } restore_{in_region_, region_was};
-      Part bp[2];
-      const int nb = chain_parts(x->rows, bp);
       bool acc;
       float* dx = gradbuf(x, acc);
       const bool fuse = fuse_cand && !x->gpre_h;
       float* scratch = alloc((long)s2st_layernorm_bwd_blocks(x->rows, x->cols) * (fuse ? 3 : 2) * x->cols);
-      float* scratch1 = nb == 2 ? alloc((long)s2st_layernorm_bwd_blocks(x->rows, x->cols) * (fuse ? 3 : 2) * x->cols) : nullptr;
       bf16raw* dph = nullptr;
       if (fuse) dph = x->gpre_h = alloc_h(x->n());
       float* dbias = fuse && x->drop2_bias >= 0 ? G + x->drop2_bias : nullptr;
       if (live()) {
-        if (nb == 2) ensure_forked();
+        auto pass = [&](int phase, hipStream_t st) {
+          chk(s2st_layernorm_bwd(y->g, x->d, P + pp.g, mean, rstd, dx, acc ? 1 : 0, G + pp.g, G + pp.b, scratch, x->rows, x->cols,
+                                 st, phase, dph, x->drop2_p, x->drop2_seed, dbias));
+        };
         if (!ln_bwd_split) {
           // one row kernel on the data path (dx, the fused bf16 operand, and the column-sum partials of dgamma / dbeta /
           // dbias); the partials of the segment's layer norms are folded together (flush_lnfold)
-          for (int ci = 0; ci < nb; ++ci) {
-            const long r0 = bp[ci].r0, o = r0 * x->cols;
-            float* sc = ci == 0 ? scratch : scratch1;
-            chk(s2st_layernorm_bwd(y->g + o, x->d + o, P + pp.g, mean + r0, rstd + r0, dx + o, acc ? 1 : 0, G + pp.g, G + pp.b, sc,
-                                   bp[ci].nr, x->cols, bp[ci].st, 3, dph ? dph + o : nullptr, x->drop2_p, x->drop2_seed ^ bp[ci].salt,
-                                   dbias));
-            if (pending_lnfold.n == S2ST_LNFOLD_MAX) flush_lnfold();
-            chk(s2st_lnfold_add(pending_lnfold, sc, bp[ci].nr, x->cols, fuse ? 3 : 2, G + pp.g, G + pp.b, dbias));
-          }
+          pass(3, st_);
+          if (pending_lnfold.n == S2ST_LNFOLD_MAX) flush_lnfold();
+          chk(s2st_lnfold_add(pending_lnfold, scratch, x->rows, x->cols, fuse ? 3 : 2, G + pp.g, G + pp.b, dbias));
         } else {
-          // S2ST_LN_BWD_SPLIT=1 (A/B switch): dx row kernel on the data path (per chain), then a second pass over dy and x
-          // for the parameter gradients + its fold on the second stream (or behind it without one)
-          auto pass = [&](int ci, int phase, hipStream_t st) {
-            const long r0 = bp[ci].r0, o = r0 * x->cols;
-            chk(s2st_layernorm_bwd(y->g + o, x->d + o, P + pp.g, mean + r0, rstd + r0, dx + o, acc ? 1 : 0, G + pp.g, G + pp.b,
-                                   ci == 0 ? scratch : scratch1, bp[ci].nr, x->cols, st, phase, dph ? dph + o : nullptr, x->drop2_p,
-                                   x->drop2_seed ^ bp[ci].salt, dbias));
-          };
-          for (int ci = 0; ci < nb; ++ci) pass(ci, 1, bp[ci].st);
-          hipStream_t rs = side_ ? fork_side() : (sync_chains(), st_);
-          for (int ci = 0; ci < nb; ++ci) pass(ci, 2, rs);
+          // S2ST_LN_BWD_SPLIT=1 (A/B switch): dx row kernel on the data path, then a second pass over dy and x for the
+          // parameter gradients + its fold on the second stream (or behind it without one)
+          pass(1, st_);
+          pass(2, side_ ? fork_side() : st_);
         }
       }
     });
-    set_aware();
     return y;
   }
 
@@ -312,36 +260,13 @@
       fa.o = o->d; fa.oh = o->h; fa.lse = lse; fa.klen = klen;
       fa.B = B; fa.H = H; fa.T = T; fa.S = S; fa.dh = dh; fa.causal = causal;
       fa.scale = 1.0f / sqrtf((float)dh); fa.drop_p = drop_p; fa.seed = sd; fa.ld_drop = ld;
-      // one chain's share of the batch: utterances [b0, b0 + nbat) of every per-utterance array
-      auto chain_args = [=](s2st_attn_args a, int b0, int nbat, uint64_t salt) {
-        a.q += (long)b0 * T * a.ldq; a.k += (long)b0 * S * a.ldk; a.v += (long)b0 * S * a.ldv;
-        if (a.o) a.o += (long)b0 * T * C; if (a.oh) a.oh += (long)b0 * T * C;
-        a.lse += (long)b0 * H * T; if (a.klen) a.klen += b0;
-        if (a.doh) a.doh += (long)b0 * T * C;
-        if (a.dq) a.dq += (long)b0 * T * a.ldq; if (a.dk) a.dk += (long)b0 * S * a.ldk; if (a.dv) a.dv += (long)b0 * S * a.ldv;
-        if (a.dqh) a.dqh += (long)b0 * T * a.ldq; if (a.dkh) a.dkh += (long)b0 * S * a.ldk; if (a.dvh) a.dvh += (long)b0 * S * a.ldv;
-        a.B = nbat; a.seed ^= salt;
-        return a;
-      };
-      Part pt[2];
-      const int np = chain_parts(B * T, pt);
-      if (live())
-        for (int ci = 0; ci < np; ++ci) {
-          const s2st_attn_args a = chain_args(fa, pt[ci].r0 / T, pt[ci].nr / T, pt[ci].salt);
-          chk(s2st_flash_attn_fwd(&a, pt[ci].st));
-        }
+      if (live()) chk(s2st_flash_attn_fwd(&fa, st_));
       AttnIO io3 = io;
-      const bool region = in_region_;
       tape.push_back([=]() {
         if (!o->g) return;
-        const bool region_was = in_region_;
-        in_region_ = region;
-        struct Restore { bool& r; bool v; ~Restore() { r = v; } } restore_{in_region_, region_was};
         float* dvec = alloc((long)B * H * T);
         s2st_attn_args fb = fa;
         fb.doh = ghalf_of(o);
-        Part bp[2];
-        const int nb = chain_parts(B * T, bp);
         // q / k / v are column blocks of plain projections: their gradients are only ever read as bf16
         // GEMM operands (+ bias column sums), so the kernels emit exactly that and no fp32 gradient
         const bool gf = use_attn_gfuse && io3.qt->lin_plain && io3.kt->lin_plain && io3.vt->lin_plain &&
@@ -366,28 +291,22 @@
         // =2: the same sums as fp32 atomics per head column (contention: slow); =3: column sums of the rounded bf16
         // copies (round 1's form: a rounding residue of ~1e-5 instead of ~0)
         const bool gf_db = gf && attn_gfuse_mode != 3;
-        float* dbp[2] = {nullptr, nullptr};
+        float* dbp = nullptr;
         if (gf_db) {
           if (io3.qt->act_bias >= 0) fb.dbq = G + io3.qt->act_bias + io3.qoff;
           if (io3.kt->act_bias >= 0) fb.dbk = G + io3.kt->act_bias + io3.koff;
           if (io3.vt->act_bias >= 0) fb.dbv = G + io3.vt->act_bias + io3.voff;
-          if (attn_gfuse_mode != 2)
-            for (int ci = 0; ci < nb; ++ci) dbp[ci] = alloc(s2st_flash_attn_db_scratch_floats(&fb));  // (sized for the whole batch)
+          if (attn_gfuse_mode != 2) dbp = alloc(s2st_flash_attn_db_scratch_floats(&fb));
         }
-        for (int ci = 0; ci < nb; ++ci) {
-          const int b0 = bp[ci].r0 / T, nbat = bp[ci].nr / T;
-          const s2st_attn_args a = chain_args(fb, b0, nbat, bp[ci].salt);
-          if (live()) chk(s2st_flash_attn_bwd(&a, o->g + (long)b0 * T * C, dvec + (long)b0 * H * T, bp[ci].st, 0, dbp[ci]));
-          if (dbp[ci] && live()) {
-            // parameter gradients: the partials join the segment's batched fold (flush_lnfold, second stream)
-            int sq = 0, sk = 0;
-            s2st_flash_attn_db_layout(&a, &sq, &sk);
-            const int Cm = a.H * a.dh;
-            if (pending_lnfold.n + 3 > S2ST_LNFOLD_MAX) flush_lnfold();
-            if (a.dbq) chk(s2st_fold_add(pending_lnfold, dbp[ci], sq, Cm, 1, a.dbq, nullptr, nullptr));
-            if (a.dbk) chk(s2st_fold_add(pending_lnfold, dbp[ci] + (long)sq * Cm, sk, Cm, 1, a.dbk, nullptr, nullptr));
-            if (a.dbv) chk(s2st_fold_add(pending_lnfold, dbp[ci] + (long)(sq + sk) * Cm, sk, Cm, 1, a.dbv, nullptr, nullptr));
-          }
+        if (live()) chk(s2st_flash_attn_bwd(&fb, o->g, dvec, st_, 0, dbp));
+        if (dbp && live()) {
+          // parameter gradients: the partials join the segment's batched fold (flush_lnfold, second stream)
+          int sq = 0, sk = 0;
+          s2st_flash_attn_db_layout(&fb, &sq, &sk);
+          if (pending_lnfold.n + 3 > S2ST_LNFOLD_MAX) flush_lnfold();
+          if (fb.dbq) chk(s2st_fold_add(pending_lnfold, dbp, sq, C, 1, fb.dbq, nullptr, nullptr));
+          if (fb.dbk) chk(s2st_fold_add(pending_lnfold, dbp + (long)sq * C, sk, C, 1, fb.dbk, nullptr, nullptr));
+          if (fb.dbv) chk(s2st_fold_add(pending_lnfold, dbp + (long)(sq + sk) * C, sk, C, 1, fb.dbv, nullptr, nullptr));
         }
         if (gf && !gf_db) {
           // projection bias gradients = column sums of the bf16 gradients: parameter gradients only, so
@@ -406,10 +325,8 @@
           }
         }
       });
-      set_aware();
       return o;
     }
-    if (live()) sync_chains();  // (the unfused path below works on whole-batch score tensors)
     float* p = alloc((long)B * H * T * ld);
     float* pd = drop_p > 0.f ? alloc((long)B * H * T * ld) : p;
     bf16raw* pdh = fm ? alloc_h((long)B * H * T * ld) : nullptr;  // bf16 dropout(p): the P*V / dV operand
@@ -503,7 +420,6 @@
     Ten* kv = kv_pre ? kv_pre : cross_kv(encx, a, C);
     if (kv_pre && kv_wait_) {  // first consumer of the projections issued on the second stream
       wait_traced(st_, ev_kv_, "cross-attention K|V projections");
-      chains_wait(ev_kv_);
       kv_wait_ = false;
     }
     AttnIO io{q, 0, C, kv, 0, 2 * C, kv, C, 2 * C};

@@ -36,14 +36,14 @@
   bf16raw* half_of(Ten* t) {
     if (!t->h) {
       t->h = alloc_h((long)t->rows * t->hld());
-      if (live()) { sync_chains(); chk(s2st_cast_bf16_rows(t->d, t->cols, t->h, t->hld(), t->rows, t->cols, st_)); }
+      if (live()) chk(s2st_cast_bf16_rows(t->d, t->cols, t->h, t->hld(), t->rows, t->cols, st_));
     }
     return t->h;
   }
   bf16raw* ghalf_of(Ten* t) {
     if (!t->gh) {
       t->gh = alloc_h((long)t->rows * t->hld());
-      if (live()) { sync_chains(); chk(s2st_cast_bf16_rows(t->g, t->cols, t->gh, t->hld(), t->rows, t->cols, st_)); }
+      if (live()) chk(s2st_cast_bf16_rows(t->g, t->cols, t->gh, t->hld(), t->rows, t->cols, st_));
     }
     return t->gh;
   }
@@ -103,7 +103,6 @@
     if (!live()) return;
     while (adam_next < (int)adam_lo.size() && adam_lo[adam_next] < off_end) {
       hipStreamWaitEvent(st_, adam_ev[adam_next], 0);  // (st_ is the data-path stream here: touch() skips the second one)
-      chains_wait(adam_ev[adam_next]);  // (a second chain forked earlier reads the same parameters)
       ++adam_next;
     }
     if (adam_next >= (int)adam_lo.size()) adam_pending = false;
@@ -163,7 +162,6 @@
     if (pending_wgrad.empty()) return;
     if (live()) {
       // everything the products read was enqueued on st_ before this point
-      if (!side_) sync_chains();
       hipStream_t s = (side_ && st_ != side_) ? fork_side() : st_;
       // S2ST_TIMING_SKIP_WGRAD=1 (-DS2ST_EXPERIMENTAL builds only: it makes the gradients WRONG): a timing experiment --
       // how much of the step is the weight-gradient products' share of the chip
@@ -190,7 +188,6 @@
   void flush_lnfold() {
     if (pending_lnfold.n == 0) return;
     if (live()) {
-      if (!side_) sync_chains();
       hipStream_t s = (side_ && st_ != side_) ? fork_side() : st_;
       chk(s2st_layernorm_bwd_fold(pending_lnfold, s));
     }

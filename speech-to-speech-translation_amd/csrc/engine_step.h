@@ -11,9 +11,6 @@
     for (Ten* t : tens) delete t;
     tens.clear();
     tape.clear();
-    tape_aware.clear();
-    forked_ = false;
-    in_region_ = false;
     marks.clear();
     ws_top = 0;
     ws_peak = 0;
@@ -70,10 +67,6 @@
     const bool with_loss = bt.tgt != nullptr;
     seed = bt.seed;
     if (tr) ensure_side();  // (also in the dry run that sizes the workspace: same stream set, same allocations)
-    main_ = st_;
-    forked_ = false;
-    in_region_ = false;
-    const bool two_chains = nchains == 2 && chain1_ && tr && fast();  // (training step only; see the note at chain_count)
     dec_overlap = s2st_env_int("S2ST_DEC_OVERLAP", 3);
 
     // sinusoidal tables come from the host side (cached per dim); conv weight layouts are
@@ -94,7 +87,6 @@
     skws_n = fm ? (long)16 << 20 : 0;
     skws = fm ? alloc(skws_n) : nullptr;
     skws_side = fm && side_allowed ? alloc(skws_n) : skws;  // (by permission, not by existence: the stream is made lazily)
-    skws_c1 = fm && chain1_ && nchains == 2 ? alloc(skws_n) : skws;
     // stream-K scratch of the persistent GEMM kernel, one per stream (ticket counters zeroed here, before any fork)
     if (fm && tr && use_streamk) {
       float* sk0 = alloc(S2ST_STREAMK_SCRATCH_FLOATS);
@@ -144,7 +136,7 @@
     //  the emulator's events are null handles, so there the block is issued ahead while all K|V projections stay on the
     //  data-path label; the emulator checks the block's re-ordered issue, the layer-0 / layers-1.. split only runs on a GPU.)
     const bool kv_side_ok = side_ && side_events_ && hoist_kv && !stop_after_encoder;
-    const bool dec_early = tr && fm && (dec_overlap & 1) && kv_side_ok && !two_chains && !c.text_input && !c.s2t_mode &&
+    const bool dec_early = tr && fm && (dec_overlap & 1) && kv_side_ok && !c.text_input && !c.s2t_mode &&
                            c.dec_layers > 0 && bt.prev && !(dec_spk >= 0 && bt.speaker);
     struct {
       std::vector<std::function<void()>> tape;
@@ -185,7 +177,6 @@
       early.site_hi = site;
       early.tape.assign(std::make_move_iterator(tape.begin() + t0), std::make_move_iterator(tape.end()));
       tape.resize(t0);
-      if (tape_aware.size() > t0) tape_aware.resize(t0);
       early.log.assign(site_log.begin() + l0, site_log.end());
       site_log.resize(l0);
       site = site0;
@@ -242,7 +233,6 @@
     mark();
     // ---- encoder layers, taps -----------------------------------------------------------------
     Ten *tap_asr = nullptr, *tap_st = nullptr;
-    in_region_ = two_chains;  // ---- two utterance-half chains: the encoder layers + the final layer norm
     for (int i = 0; i < c.enc_layers; ++i) {
       set_ctx("enc.L%d", i);
       x = enc_layer(x, enc[i], B, E);
@@ -252,8 +242,6 @@
     }
     const bool t2s_spk = c.text_input && enc_spk >= 0 && bt.speaker != nullptr;
     Ten* enc_out = has_enc_ln ? layernorm(x, enc_ln, t2s_spk ? nullptr : outs.enc_out) : x;
-    in_region_ = false;
-    if (live()) sync_chains();
     if (t2s_spk) {
       // t2s_transformer.py:107-111: x = spk_emb_proj(cat[x, emb.expand(T)]) on EVERY position (padded ones included),
       // after the final layer norm.  The concatenation is materialised so that forward, data gradient and weight
@@ -348,7 +336,6 @@
     Ten* y = nullptr;
     auto file_early = [&](size_t lo, size_t hi, long wm) {  // closures [lo, hi) of the block issued ahead take their place
       for (size_t k = lo; k < hi; ++k) tape.push_back(std::move(early.tape[k]));
-      tape_aware.resize(tape.size(), 0);
       if (wm > param_watermark) param_watermark = wm;
     };
     if (dec_early) {
@@ -370,7 +357,6 @@
     }
     mark();
     if (dec_early) file_early(early.n_front, early.tape.size(), early.wm_head);
-    in_region_ = two_chains;  // ---- two chains again: decoder layers, final layer norm, the two output projections
     float* attn_out = nullptr;
     Ten* tap_dec_t = nullptr;
     for (int i = 0; i < c.dec_layers; ++i) {
@@ -385,15 +371,13 @@
     (void)attn_out;
     // S2ST_DEC_OVERLAP bit 1: the backward's share (backward_segment).  With the projections hoisted, layer 0's query
     // projection is the closure right below its cross-attention's.
-    if (tr && kv_side_ok && live() && !two_chains && (dec_overlap & 2) && xattn0_idx > tail_lo_idx) {
+    if (tr && kv_side_ok && live() && (dec_overlap & 2) && xattn0_idx > tail_lo_idx) {
       tail_hi_idx = xattn0_idx;
       tail_bwd_on_side = true;
     }
     if (has_dec_ln) y = layernorm(y, dec_ln);
     Ten* feat = linear(y, feat_proj.w, feat_proj.b, c.out_dim, Cd, 0, 0.f, nullptr, outs.feat);
     Ten* eos = linear(y, eos_proj.w, eos_proj.b, 1, Cd, 0, 0.f, nullptr, outs.eos);
-    in_region_ = false;
-    if (live()) sync_chains();
     set_ctx("post");
     Ten* post = postnet(feat, B, D, tr, csp, outs.post_feat);
     set_ctx("");
@@ -583,8 +567,6 @@
     if (seg == 0) join_side();  // transposed weights (and anything else the forward left on the side stream)
     size_t hi = marks[ns - seg].tape_idx, lo = marks[ns - seg - 1].tape_idx;
     hipStream_t main_st = st_;
-    main_ = st_;
-    in_region_ = false;
     for (size_t i = hi; i-- > lo;) {
       if (aux_bwd_on_side && live()) {
         // the aux decoders' backward (CTC head + text decoders: many small kernels that only produce
@@ -607,8 +589,6 @@
         if (in_tail && st_ == main_st) { st_ = fork_side(); tail_side_ = true; }
         if (!in_tail && tail_side_) { st_ = main_st; tail_side_ = false; }
       }
-      // (a closure that does not launch per chain itself sees everything the second chain did)
-      if (live() && !(i < tape_aware.size() && tape_aware[i])) sync_chains();
       tape[i]();
       if (err) break;
     }
@@ -619,7 +599,6 @@
       st_ = main_st;
     }
     tail_side_ = false;
-    if (live()) sync_chains();  // (the caller's stream is the one the next segment / the optimizer continues on)
     // The segment's weight gradients live on the second stream.  A caller that overlaps the gradient
     // all-reduce waits on that stream itself (s2st_engine_side_stream); the data path only joins once,
     // after the last segment, so it never stalls behind the weight-gradient backlog.

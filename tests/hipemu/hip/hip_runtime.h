@@ -207,9 +207,9 @@ static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMem
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return hipSuccess; }
 enum { hipStreamNonBlocking = 1, hipEventDisableTiming = 2 };
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return hipSuccess; }
-// (every launch of the emulator is synchronous: a second stream is only a label -- enough for the engine's two-chain
-//  schedule, S2ST_CHAINS=2, whose partition of rows / seeds / scratch is what the emulator can check; the priority form,
-//  which the engine's weight-gradient stream uses, stays unavailable)
+// (every launch of the emulator is synchronous: a second stream is only a label -- this plain form is what gives the
+//  emulator the engine's side-stream schedule, whose issue order is what it can check (ensure_side falls back to it); the
+//  priority form, which the engine asks for first, stays unavailable)
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { static char tag; *s = (hipStream_t)&tag; return hipSuccess; }
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = nullptr; return hipErrorInvalidValue; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) { *least = 0; *greatest = 0; return hipSuccess; }
