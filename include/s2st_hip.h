@@ -728,7 +728,8 @@ int s2st_beam_poll(const void* state, void* host_out_64_bytes, void* stream);
 
 /* ---- frozen HuBERT front end of config 4 (--use-hubert): fairseq/models/hubert/hubert.py:412-461,
  * 518-534 (extract_features, eval, mask=False) with wav2vec2.py:736-905.  The handle is an
- * s2st_engine in "hubert mode": parameters are enumerated / bound with s2st_engine_param_info,
+ * s2st_engine of the speech-encoder kind, group-norm / post-LN variant: parameters are enumerated /
+ * bound with s2st_engine_param_info,
  * s2st_engine_bind(params, NULL, NULL) and s2st_engine_bind_bf16; conv weights are stored in GEMM
  * layout [O][k][I] and the weight-normed pos_conv as its effective weight [G][E/G][k][E/G] (the host
  * wrapper converts from the reference state_dict).  Forward only. */
@@ -775,7 +776,8 @@ int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames
  * through transformers -- Wav2Vec2Processor's zero-mean / unit-variance normalisation, Wav2Vec2ForCTC (feat_extract_norm
  * "layer", do_stable_layer_norm: conv + bias -> LayerNorm over channels -> GELU seven times, LayerNorm -> projection,
  * x += GELU(pos_conv(x)), pre-LN transformer layers, final LayerNorm, lm_head), torch.argmax and the CTC tokenizer's
- * collapse.  The handle is an s2st_engine in "w2v_ctc mode": parameters are enumerated / bound with
+ * collapse.  The handle is an s2st_engine of the speech-encoder kind (the HuBERT front end's), layer-norm / pre-LN
+ * variant: parameters are enumerated / bound with
  * s2st_engine_param_info, s2st_engine_bind(params, NULL, NULL) and s2st_engine_bind_bf16 under the transformers
  * state_dict names; conv weights are stored [O][k][I] and the weight-normed pos_conv as its effective weight
  * [G][E/G][k][E/G] (the host wrapper converts).  Forward only. */

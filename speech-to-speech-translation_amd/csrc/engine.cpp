@@ -14,6 +14,7 @@
 // Layout: activations are [B][T][C] row-major (the reference is [T][B][C]); padded rows are
 // computed exactly as the reference computes them.
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -227,13 +228,11 @@ struct s2st_engine {
   // S2ST_CONVNET_FUSE=0 (A/B switch): BatchNorm statistics finalize / backward fold / the convolutions' gradient halo
   // images / the post-net residual add as launches of their own
   bool convnet_fuse = s2st_env_int("S2ST_CONVNET_FUSE", 1) != 0;
-  int ffn_act = 1;        // 1 relu (s2st layers), 2 gelu (HuBERT layers)
-  // ---- frozen HuBERT front end (config 4): same engine object in "hubert mode" -------------
-  bool is_hubert = false;
-  s2st_hubert_config hc{};
-  struct HubP {
-    long conv_w[8]; long gn_g, gn_b; LNP ln; LinP proj; long pos_w, pos_b; std::vector<EncLayerP> L; LNP enc_ln;
-  } hp;
+  int ffn_act = 1;        // 1 relu (s2st layers), 2 gelu (the speech encoders' layers)
+  // what the handle was created as: the s2st / s2t transformer, or one of the frozen forward-only networks in the same
+  // engine object (engine_speech_encoder.h, engine_hifigan.h)
+  enum class Kind { Transformer, SpeechEncoder, HifiGan };
+  Kind kind = Kind::Transformer;
   float* ws_for(hipStream_t s) const { return (side_ && s == side_) ? skws_side : skws; }
   float* skws = nullptr;  // split-K partial-sum scratch of the weight-gradient GEMMs (per call)
   long skws_n = 0;
@@ -307,11 +306,9 @@ struct s2st_engine {
 
 #include "engine_convnets.h"  // the convolutional sub-networks
 
-#include "engine_hubert.h"  // the frozen HuBERT front end (config 4)
+#include "engine_speech_encoder.h"  // the frozen HuBERT front end (config 4) and the wav2vec 2.0 CTC recogniser (ASR-BLEU)
 
 #include "engine_hifigan.h"  // the HiFi-GAN vocoder (--vocoder hifigan)
-
-#include "engine_w2v_ctc.h"  // the wav2vec 2.0 CTC recogniser (ASR-BLEU)
 
 #include "engine_step.h"  // one step
 
@@ -351,6 +348,50 @@ s2st_batch eval_batch(int B, int E, const int32_t* enc_lens) {
 
 bool aux_args_ok(const s2st_engine* e, int which) {
   return e && which >= 0 && which <= 1 && !((which == 0 && !e->c.has_asr) || (which == 1 && !e->c.has_st));
+}
+
+// The two speech encoders' one create (engine_speech_encoder.h): cfg.vocab is read by the LayerNormPreLN variant only.
+int speech_encoder_create(const s2st_w2v_ctc_config& cfg, s2st_engine::SpeechVariant v, s2st_engine** out) {
+  const bool pre_ln = v == s2st_engine::SpeechVariant::LayerNormPreLN;
+  if (cfg.n_conv < 1 || cfg.n_conv > 8 || (pre_ln && cfg.vocab < 1) || cfg.layers < 0 || cfg.heads < 1 ||
+      cfg.conv_pos_groups < 1 || cfg.conv_pos < 1)
+    return S2ST_ERR_ARG;
+  if (cfg.embed % cfg.heads || cfg.embed % cfg.conv_pos_groups || (cfg.embed / cfg.conv_pos_groups) % 4 || cfg.embed % 4)
+    return S2ST_ERR_SHAPE;
+  for (int i = 0; i < cfg.n_conv; ++i)
+    if (cfg.conv_k[i] < 1 || cfg.conv_stride[i] < 1) return S2ST_ERR_SHAPE;
+  // what the variant's kernels take: conv 0 (s2st_hubert_conv0_gn_gelu / s2st_w2v_conv0_ln_gelu) and, LayerNormPreLN, the
+  // row kernel behind every later convolution (s2st_w2v_ln_gelu_rows)
+  if (!pre_ln && cfg.conv_dim[0] % 4) return S2ST_ERR_SHAPE;
+  if (pre_ln && (cfg.conv_dim[0] > 512 || cfg.conv_k[0] > 16)) return S2ST_ERR_SHAPE;
+  for (int i = 0; pre_ln && i < cfg.n_conv; ++i)
+    if (cfg.conv_dim[i] < 4 || cfg.conv_dim[i] % 4 || cfg.conv_dim[i] > 1024) return S2ST_ERR_SHAPE;
+  if (!cfg.precise) {
+    for (int i = 0; i < cfg.n_conv; ++i)
+      if (cfg.conv_dim[i] % 8) return S2ST_ERR_SHAPE;
+    if (cfg.embed % 8 || cfg.ffn % 8 || (cfg.embed / cfg.conv_pos_groups) % 8) return S2ST_ERR_SHAPE;
+  }
+  s2st_engine* e = new s2st_engine();
+  e->kind = s2st_engine::Kind::SpeechEncoder;
+  e->sv = v;
+  e->sc = cfg;
+  e->c = s2st_model_config{};
+  e->c.precise = cfg.precise;
+  e->c.enc_heads = cfg.heads;
+  e->c.enc_dim = cfg.embed;
+  e->ffn_act = 2;
+  // the recogniser: every product goes through the tiled GEMM whatever the batch's row count: an utterance's logits do not
+  // depend on what else is in the batch
+  if (pre_ln) e->use_skinny = false;
+  e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
+  e->use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
+  e->build_params_speech();
+  // (a process that replays HIP graphs can carry a stale "last error" of the runtime's own capture-time queries: the preload's
+  //  launch checks must see their own errors only)
+  (void)hipGetLastError();
+  if (!cfg.precise && (s2st_gemm_bf16_preload(nullptr) != 0 || s2st_flash_attn_preload(nullptr) != 0)) { delete e; return S2ST_ERR_LAUNCH; }
+  *out = e;
+  return 0;
 }
 }  // namespace
 
@@ -773,53 +814,60 @@ int64_t s2st_engine_aux_decode_workspace(s2st_engine* e, int32_t which, int32_t 
   });
 }
 
-// ---- HuBERT front end ---------------------------------------------------------------------------
+// ---- the speech encoders: HuBERT front end, wav2vec 2.0 CTC recogniser -----------------------------
 int s2st_hubert_create(const s2st_hubert_config* cfg, s2st_engine** out) {
-  if (!cfg || !out || cfg->n_conv < 1 || cfg->n_conv > 8) return S2ST_ERR_ARG;
-  if (cfg->embed % cfg->heads || cfg->embed % cfg->conv_pos_groups || cfg->conv_dim[0] % 4 ||
-      (cfg->embed / cfg->conv_pos_groups) % 4 || cfg->embed % 4)
-    return S2ST_ERR_SHAPE;
-  if (!cfg->precise) {
-    for (int i = 0; i < cfg->n_conv; ++i)
-      if (cfg->conv_dim[i] % 8) return S2ST_ERR_SHAPE;
-    if (cfg->embed % 8 || cfg->ffn % 8 || (cfg->embed / cfg->conv_pos_groups) % 8) return S2ST_ERR_SHAPE;
-  }
-  s2st_engine* e = new s2st_engine();
-  e->is_hubert = true;
-  e->hc = *cfg;
-  e->c = s2st_model_config{};
-  e->c.precise = cfg->precise;
-  e->c.enc_heads = cfg->heads;
-  e->c.enc_dim = cfg->embed;
-  e->ffn_act = 2;
-  e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
-  e->use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
-  e->build_params_hubert();
-  // (a process that replays HIP graphs can carry a stale "last error" of the runtime's own capture-time queries: the preload's
-  //  launch checks must see their own errors only)
-  (void)hipGetLastError();
-  if (!cfg->precise && (s2st_gemm_bf16_preload(nullptr) != 0 || s2st_flash_attn_preload(nullptr) != 0)) { delete e; return S2ST_ERR_LAUNCH; }
-  *out = e;
-  return 0;
+  if (!cfg || !out) return S2ST_ERR_ARG;
+  static_assert(offsetof(s2st_w2v_ctc_config, vocab) == sizeof(s2st_hubert_config), "s2st_hubert_config is the prefix");
+  s2st_w2v_ctc_config full{};
+  memcpy(&full, cfg, sizeof(*cfg));
+  return speech_encoder_create(full, s2st_engine::SpeechVariant::GroupNormPostLN, out);
 }
 
-int32_t s2st_hubert_out_frames(const s2st_engine* e, int32_t n_samples) { return e->hubert_frames(n_samples); }
+int32_t s2st_hubert_out_frames(const s2st_engine* e, int32_t n_samples) { return e->speech_frames(n_samples); }
 
 int64_t s2st_hubert_workspace_floats(s2st_engine* e, int32_t B, int32_t N) {
-  if (!e->is_hubert) return S2ST_ERR_ARG;
-  return dry_run_floats(e, [&] { return e->forward_hubert(nullptr, nullptr, B, N, nullptr); });
+  if (!e->is_speech(s2st_engine::SpeechVariant::GroupNormPostLN)) return S2ST_ERR_ARG;
+  return dry_run_floats(e, [&] { return e->forward_speech(nullptr, nullptr, nullptr, B, N, nullptr, 0, nullptr, nullptr); });
 }
 
 int s2st_hubert_forward(s2st_engine* e, const float* wave, const int32_t* frame_lens, int32_t B, int32_t N, float* out,
                         float* workspace, int64_t workspace_floats, void* stream) {
-  if (!e->is_hubert || !e->P || !wave || !frame_lens || !out) return S2ST_ERR_ARG;
+  if (!e->is_speech(s2st_engine::SpeechVariant::GroupNormPostLN) || !e->P || !wave || !frame_lens || !out) return S2ST_ERR_ARG;
   e->begin_call(workspace, workspace_floats, stream);
   // frozen weights: the host side tracks the parameter tensor's version and vouches for the bf16 copy (0.1 ms of the
   // 6.9 ms forward); forward only: the front end is frozen (s2st_transformer.py:245-249)
   if (int rc = e->params_ready()) return rc;
-  return e->end_call(e->forward_hubert(wave, frame_lens, B, N, out));
+  return e->end_call(e->forward_speech(wave, nullptr, frame_lens, B, N, out, 0, nullptr, nullptr));
 }
 
+int s2st_w2v_ctc_create(const s2st_w2v_ctc_config* cfg, s2st_engine** out) {
+  if (!cfg || !out) return S2ST_ERR_ARG;
+  return speech_encoder_create(*cfg, s2st_engine::SpeechVariant::LayerNormPreLN, out);
+}
+
+int32_t s2st_w2v_ctc_out_frames(const s2st_engine* e, int32_t n_samples) {
+  if (!e || !e->is_speech(s2st_engine::SpeechVariant::LayerNormPreLN)) return S2ST_ERR_ARG;
+  return e->speech_frames(n_samples);
+}
+
+int64_t s2st_w2v_ctc_workspace_floats(s2st_engine* e, int32_t B, int32_t N) {
+  if (!e || !e->is_speech(s2st_engine::SpeechVariant::LayerNormPreLN) || B <= 0 || N <= 0) return S2ST_ERR_ARG;
+  // (logits: the dry workspace, never dereferenced; the collapse allocates nothing)
+  return dry_run_floats(e, [&] { return e->forward_speech(nullptr, nullptr, nullptr, B, N, e->ws, 0, nullptr, nullptr); });
+}
+
+int s2st_w2v_ctc_forward(s2st_engine* e, const float* wave, const int32_t* sample_lens, const int32_t* frame_lens, int32_t B,
+                         int32_t N, int32_t blank, float* logits_out, int32_t* ids_out, int32_t* counts_out,
+                         float* workspace, int64_t workspace_floats, void* stream) {
+  if (!e || !e->is_speech(s2st_engine::SpeechVariant::LayerNormPreLN) || !e->P || !wave || !sample_lens || !frame_lens ||
+      !logits_out || (ids_out && !counts_out))
+    return S2ST_ERR_ARG;
+  if (B <= 0 || N <= 0) return S2ST_ERR_SHAPE;
+  if (!workspace) return S2ST_ERR_WORKSPACE;
+  e->begin_call(workspace, workspace_floats, stream);
+  if (int rc = e->params_ready()) return rc;  // (frozen weights, as in s2st_hubert_forward)
+  return e->end_call(e->forward_speech(wave, sample_lens, frame_lens, B, N, logits_out, blank, ids_out, counts_out));
+}
 
 // ---- HiFi-GAN vocoder ---------------------------------------------------------------------------
 int s2st_hifigan_create(const s2st_hifigan_config* cfg, s2st_engine** out) {
@@ -839,7 +887,7 @@ int s2st_hifigan_create(const s2st_hifigan_config* cfg, s2st_engine** out) {
       if (cfg->rb_dilations[j][l] < 1 || (cfg->rb_kernels[j] - 1) * cfg->rb_dilations[j][l] > 64) return S2ST_ERR_SHAPE;
   }
   s2st_engine* e = new s2st_engine();
-  e->is_hifigan = true;
+  e->kind = s2st_engine::Kind::HifiGan;
   e->gc = *cfg;
   e->c = s2st_model_config{};
   e->c.precise = cfg->precise;
@@ -849,80 +897,21 @@ int s2st_hifigan_create(const s2st_hifigan_config* cfg, s2st_engine** out) {
 }
 
 int64_t s2st_hifigan_out_samples(const s2st_engine* e, int32_t T) {
-  if (!e || !e->is_hifigan) return S2ST_ERR_ARG;
+  if (!e || e->kind != s2st_engine::Kind::HifiGan) return S2ST_ERR_ARG;
   return e->hifigan_samples(T);
 }
 
 int64_t s2st_hifigan_workspace_floats(s2st_engine* e, int32_t B, int32_t T_max) {
-  if (!e || !e->is_hifigan) return S2ST_ERR_ARG;
+  if (!e || e->kind != s2st_engine::Kind::HifiGan) return S2ST_ERR_ARG;
   return dry_run_floats(e, [&] { return e->forward_hifigan(nullptr, nullptr, B, T_max, nullptr); });
 }
 
 int s2st_hifigan_forward(s2st_engine* e, const float* mel, const int32_t* frames, int32_t B, int32_t T, float* wave_out,
                          float* workspace, int64_t workspace_floats, void* stream) {
-  if (!e || !e->is_hifigan || !e->P || !mel || !frames || !wave_out) return S2ST_ERR_ARG;
+  if (!e || e->kind != s2st_engine::Kind::HifiGan || !e->P || !mel || !frames || !wave_out) return S2ST_ERR_ARG;
   e->begin_call(workspace, workspace_floats, stream);
   if (int rc = e->params_ready()) return rc;  // (frozen weights, as in s2st_hubert_forward)
   return e->end_call(e->forward_hifigan(mel, frames, B, T, wave_out));
-}
-
-// ---- wav2vec 2.0 CTC recogniser -------------------------------------------------------------------
-int s2st_w2v_ctc_create(const s2st_w2v_ctc_config* cfg, s2st_engine** out) {
-  if (!cfg || !out || cfg->n_conv < 1 || cfg->n_conv > 8 || cfg->vocab < 1 || cfg->layers < 0 || cfg->heads < 1 ||
-      cfg->conv_pos_groups < 1 || cfg->conv_pos < 1)
-    return S2ST_ERR_ARG;
-  if (cfg->embed % cfg->heads || cfg->embed % cfg->conv_pos_groups || (cfg->embed / cfg->conv_pos_groups) % 4 || cfg->embed % 4 ||
-      cfg->conv_dim[0] > 512 || cfg->conv_k[0] > 16)
-    return S2ST_ERR_SHAPE;
-  for (int i = 0; i < cfg->n_conv; ++i)
-    if (cfg->conv_dim[i] < 4 || cfg->conv_dim[i] % 4 || cfg->conv_dim[i] > 1024 || cfg->conv_k[i] < 1 || cfg->conv_stride[i] < 1)
-      return S2ST_ERR_SHAPE;
-  if (!cfg->precise) {
-    for (int i = 0; i < cfg->n_conv; ++i)
-      if (cfg->conv_dim[i] % 8) return S2ST_ERR_SHAPE;
-    if (cfg->embed % 8 || cfg->ffn % 8 || (cfg->embed / cfg->conv_pos_groups) % 8) return S2ST_ERR_SHAPE;
-  }
-  s2st_engine* e = new s2st_engine();
-  e->is_w2v = true;
-  e->wc = *cfg;
-  e->c = s2st_model_config{};
-  e->c.precise = cfg->precise;
-  e->c.enc_heads = cfg->heads;
-  e->c.enc_dim = cfg->embed;
-  e->ffn_act = 2;
-  // every product goes through the tiled GEMM whatever the batch's row count: an utterance's logits do not depend on what
-  // else is in the batch
-  e->use_skinny = false;
-  e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
-  e->use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
-  e->build_params_w2v_ctc();
-  (void)hipGetLastError();  // (as in s2st_hubert_create)
-  if (!cfg->precise && (s2st_gemm_bf16_preload(nullptr) != 0 || s2st_flash_attn_preload(nullptr) != 0)) { delete e; return S2ST_ERR_LAUNCH; }
-  *out = e;
-  return 0;
-}
-
-int32_t s2st_w2v_ctc_out_frames(const s2st_engine* e, int32_t n_samples) {
-  if (!e || !e->is_w2v) return S2ST_ERR_ARG;
-  return e->w2v_frames(n_samples);
-}
-
-int64_t s2st_w2v_ctc_workspace_floats(s2st_engine* e, int32_t B, int32_t N) {
-  if (!e || !e->is_w2v || B <= 0 || N <= 0) return S2ST_ERR_ARG;
-  // (logits: the dry workspace, never dereferenced; the collapse allocates nothing)
-  return dry_run_floats(e, [&] { return e->forward_w2v_ctc(nullptr, nullptr, nullptr, B, N, 0, e->ws, nullptr, nullptr); });
-}
-
-int s2st_w2v_ctc_forward(s2st_engine* e, const float* wave, const int32_t* sample_lens, const int32_t* frame_lens, int32_t B,
-                         int32_t N, int32_t blank, float* logits_out, int32_t* ids_out, int32_t* counts_out,
-                         float* workspace, int64_t workspace_floats, void* stream) {
-  if (!e || !e->is_w2v || !e->P || !wave || !sample_lens || !frame_lens || !logits_out || (ids_out && !counts_out))
-    return S2ST_ERR_ARG;
-  if (B <= 0 || N <= 0) return S2ST_ERR_SHAPE;
-  if (!workspace) return S2ST_ERR_WORKSPACE;
-  e->begin_call(workspace, workspace_floats, stream);
-  if (int rc = e->params_ready()) return rc;  // (frozen weights, as in s2st_hubert_forward)
-  return e->end_call(e->forward_w2v_ctc(wave, sample_lens, frame_lens, B, N, blank, logits_out, ids_out, counts_out));
 }
 
 }  // extern "C"

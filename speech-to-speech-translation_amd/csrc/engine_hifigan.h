@@ -3,7 +3,6 @@
   // ------------------------------------------------------------------------------------
   // HiFi-GAN (fairseq/models/text_to_speech/hifigan.py:109-162): weight-norm folded on the host, conv weights
   // [C_out][k][C_in], the transposed convolutions in polyphase form [u][C_out][ceil(k/u)][C_in] (include/s2st_hip.h).
-  bool is_hifigan = false;
   s2st_hifigan_config gc{};
   struct GanConv { long w, b; int cin, cout, k, dil; };
   struct GanP { GanConv pre, post; GanConv ups[8]; std::vector<GanConv> c1, c2; } gp;  // c1 / c2: [stage][rb][layer]

@@ -13,88 +13,45 @@ frozen).
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import torch
 
 from ..runtime import binding as bd
-from ..runtime.frozen import FrozenNet
+from .speech_encoder import DEFAULT_CONV as BASE_CONV, SpeechEncoder
 
-BASE_CONV = [(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)] * 2
-
-
-class HubertConfigC(C.Structure):
-    _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_k", C.c_int32 * 8),
-                ("conv_stride", C.c_int32 * 8)] + [(n, C.c_int32) for n in (
-                    "embed", "layers", "heads", "ffn", "conv_pos", "conv_pos_groups", "precise")]
+POS_W = "encoder.pos_conv.0.weight"
 
 
-class HubertFrontend(FrozenNet):
+class HubertFrontend(SpeechEncoder):
     """hubert_base geometry by default (conv stack 7 layers, 12 x 768, 12 heads, ffn 3072, conv_pos 128/16)."""
     kind = "hubert"
+    CONV_W = ("feature_extractor.conv_layers.", ".0.weight")
+    POS_W = POS_W
+    LABEL = "HuBERT"
 
     def __init__(self, device: torch.device, conv=None, embed=768, layers=12, heads=12, ffn=3072, conv_pos=128,
                  conv_pos_groups=16, precise: bool = False):
-        self.conv = list(conv or BASE_CONV)
-        self.embed, self.layers, self.heads, self.ffn = embed, layers, heads, ffn
-        self.conv_pos, self.groups, self.precise = conv_pos, conv_pos_groups, precise
-        cfg = HubertConfigC()
-        cfg.n_conv = len(self.conv)
-        for i, (c, k, s) in enumerate(self.conv):
-            cfg.conv_dim[i], cfg.conv_k[i], cfg.conv_stride[i] = c, k, s
-        cfg.embed, cfg.layers, cfg.heads, cfg.ffn = embed, layers, heads, ffn
-        cfg.conv_pos, cfg.conv_pos_groups, cfg.precise = conv_pos, conv_pos_groups, int(precise)
-        self._create(device, cfg, precise)
+        self._create_encoder(device, conv or BASE_CONV, embed, layers, heads, ffn, conv_pos, conv_pos_groups, precise)
         self._extra: Dict[str, torch.Tensor] = {}  # reference tensors the forward does not read
 
     # -- parameters: reference names / layouts <-> engine arena ------------------------------------
-    def reference_shapes(self) -> Dict[str, Tuple[int, ...]]:
-        s: Dict[str, Tuple[int, ...]] = {}
-        for n, _, _, shape in self.infos:
-            if n.startswith("feature_extractor.conv_layers.") and n.endswith(".0.weight"):
-                s[n] = (shape[0], shape[2], shape[1])  # engine [O][k][I] <- reference [O][I][k]
-            elif n == "encoder.pos_conv.0.weight":
-                Eg = self.embed // self.groups
-                s["encoder.pos_conv.0.weight_g"] = (1, 1, self.conv_pos)
-                s["encoder.pos_conv.0.weight_v"] = (self.embed, Eg, self.conv_pos)
-            else:
-                s[n] = shape
-        return s
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        need = self.reference_shapes()
-        missing = [k for k in need if k not in sd]
-        if missing and strict:
-            raise KeyError(f"missing HuBERT tensors: {missing[:5]}")
-        dev = self.device
-        for n, _, _, shape in self.infos:
-            if n == "encoder.pos_conv.0.weight":
-                g = sd["encoder.pos_conv.0.weight_g"].to(dev, torch.float32)
-                v = sd["encoder.pos_conv.0.weight_v"].to(dev, torch.float32)
-                self._extra["encoder.pos_conv.0.weight_g"] = g.clone()
-                self._extra["encoder.pos_conv.0.weight_v"] = v.clone()
-                # nn.utils.weight_norm(dim=2): w[:, :, k] = g[k] * v[:, :, k] / ||v[:, :, k]||_F
-                # (wav2vec2.py:836).  A one-off host-side parameter fold of a frozen module.
-                w = g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
-                G, Eg = self.groups, self.embed // self.groups
-                self._view(n).copy_(w.view(G, Eg, Eg, self.conv_pos).permute(0, 1, 3, 2))
-            elif n.startswith("feature_extractor.conv_layers.") and n.endswith(".0.weight"):
-                self._view(n).copy_(sd[n].to(dev, torch.float32).permute(0, 2, 1))
-            else:
-                self._view(n).copy_(sd[n].to(dev, torch.float32).view(shape))
+        need = self._needed(sd, strict)
+        self._copy_in(sd)
+        for k in (POS_W + "_g", POS_W + "_v"):  # (the engine keeps only the folded weight: state_dict() hands these back)
+            self._extra[k] = sd[k].to(self.device, torch.float32).clone()
         for k, v in sd.items():
             if k not in need:
                 self._extra[k] = v.detach().clone()
-        self.invalidate_bf16()  # (explicit: the copies above also bump torch's version counter)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         out: Dict[str, torch.Tensor] = {}
         for n, _, _, shape in self.infos:
-            if n == "encoder.pos_conv.0.weight":
+            if n == POS_W:
                 continue
             v = self._view(n)
-            if n.startswith("feature_extractor.conv_layers.") and n.endswith(".0.weight"):
+            if self._is_conv_w(n):
                 v = v.permute(0, 2, 1).contiguous()
             out[n] = v.clone()
         out.update({k: v.clone() for k, v in self._extra.items()})
@@ -125,9 +82,6 @@ class HubertFrontend(FrozenNet):
         ev.record()
         buf[1] = ev
         return out
-
-    def out_frames(self, n_samples: int) -> int:
-        return int(self.lib.s2st_hubert_out_frames(self.h, n_samples))
 
     @staticmethod
     def frame_padding_mask(padding_mask: torch.Tensor, n_frames: int) -> torch.Tensor:

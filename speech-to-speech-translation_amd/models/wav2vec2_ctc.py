@@ -28,7 +28,6 @@ hand to compare against.  Output length ``ceil(n * to / from)``.
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import math
 import os
@@ -39,20 +38,13 @@ import numpy as np
 import torch
 
 from ..runtime import binding as bd
-from ..runtime.frozen import FrozenNet
+from .speech_encoder import DEFAULT_CONV as LARGE_CONV, SpeechEncoder
 
 REFERENCE_MODEL = "facebook/wav2vec2-large-960h-lv60-self"
-LARGE_CONV = [(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)] * 2
 POS_W = "wav2vec2.encoder.pos_conv_embed.conv.weight"
 _POS_SPELLINGS = ((POS_W + "_g", POS_W + "_v"),
                   ("wav2vec2.encoder.pos_conv_embed.conv.parametrizations.weight.original0",
                    "wav2vec2.encoder.pos_conv_embed.conv.parametrizations.weight.original1"))
-
-
-class W2vCtcConfigC(C.Structure):
-    _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_k", C.c_int32 * 8),
-                ("conv_stride", C.c_int32 * 8)] + [(n, C.c_int32) for n in (
-                    "embed", "layers", "heads", "ffn", "conv_pos", "conv_pos_groups", "precise", "vocab")]
 
 
 # ---- checkpoint files ---------------------------------------------------------------------------------------------
@@ -192,27 +184,21 @@ def _default_device() -> torch.device:
 
 
 # ---- the recogniser -----------------------------------------------------------------------------------------------
-class Wav2Vec2CTC(FrozenNet):
+class Wav2Vec2CTC(SpeechEncoder):
     """wav2vec2-large-960h-lv60-self geometry by default (conv stack 7 x 512 with bias, 24 x 1024, 16 heads, ffn 4096,
     pos conv 128 taps / 16 groups, vocabulary 32)."""
     kind = "w2v_ctc"
+    CONV_W = ("wav2vec2.feature_extractor.conv_layers.", ".conv.weight")
+    POS_W = POS_W
+    LABEL = "wav2vec 2.0"
 
     def __init__(self, device=None, conv=None, embed=1024, layers=24, heads=16, ffn=4096, conv_pos=128,
                  conv_pos_groups=16, vocab=32, precise: bool = False, pad_token_id: int = 0,
                  vocab_map: Optional[Dict[str, int]] = None, word_delimiter: str = "|"):
         device = torch.device(device) if device is not None else _default_device()
-        self.conv = [tuple(int(v) for v in c) for c in (conv or LARGE_CONV)]
-        self.embed, self.layers, self.heads, self.ffn = embed, layers, heads, ffn
-        self.conv_pos, self.groups, self.vocab, self.precise = conv_pos, conv_pos_groups, vocab, bool(precise)
         self.pad_token_id, self.word_delimiter = int(pad_token_id), word_delimiter
         self.id_to_token = {int(i): t for t, i in (vocab_map or {}).items()}
-        cfg = W2vCtcConfigC()
-        cfg.n_conv = len(self.conv)
-        for i, (c, k, s) in enumerate(self.conv):
-            cfg.conv_dim[i], cfg.conv_k[i], cfg.conv_stride[i] = c, k, s
-        cfg.embed, cfg.layers, cfg.heads, cfg.ffn = embed, layers, heads, ffn
-        cfg.conv_pos, cfg.conv_pos_groups, cfg.precise, cfg.vocab = conv_pos, conv_pos_groups, int(self.precise), vocab
-        self._create(device, cfg, self.precise)
+        self._create_encoder(device, conv or LARGE_CONV, embed, layers, heads, ffn, conv_pos, conv_pos_groups, precise, vocab)
 
     @classmethod
     def from_config(cls, config: dict, vocab_map: Optional[Dict[str, int]] = None, device=None, precise: bool = False):
@@ -239,18 +225,6 @@ class Wav2Vec2CTC(FrozenNet):
         return net
 
     # -- parameters: transformers names / layouts <-> engine arena ---------------------------------------------------
-    def reference_shapes(self) -> Dict[str, Tuple[int, ...]]:
-        s: Dict[str, Tuple[int, ...]] = {}
-        for n, _, _, shape in self.infos:
-            if n.startswith("wav2vec2.feature_extractor.conv_layers.") and n.endswith(".conv.weight"):
-                s[n] = (shape[0], shape[2], shape[1])  # engine [O][k][I] <- reference [O][I][k]
-            elif n == POS_W:
-                s[POS_W + "_g"] = (1, 1, self.conv_pos)
-                s[POS_W + "_v"] = (self.embed, self.embed // self.groups, self.conv_pos)
-            else:
-                s[n] = shape
-        return s
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         sd = dict(sd)
         for g_name, v_name in _POS_SPELLINGS:
@@ -258,36 +232,12 @@ class Wav2Vec2CTC(FrozenNet):
                 g, v = sd.pop(g_name), sd.pop(v_name)
                 sd[POS_W + "_g"], sd[POS_W + "_v"] = g, v
                 break
-        need = self.reference_shapes()
-        missing = [k for k in need if k not in sd]
-        if missing and strict:
-            raise KeyError(f"missing wav2vec 2.0 tensors: {missing[:5]}")
-        for k, shape in need.items():
+        for k, shape in self._needed(sd, strict).items():
             if k in sd and tuple(sd[k].shape) != tuple(shape):
                 raise ValueError(f"{k}: shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
-        dev = self.device
-        for n, _, _, shape in self.infos:
-            if n == POS_W:
-                g = sd[POS_W + "_g"].to(dev, torch.float32)
-                v = sd[POS_W + "_v"].to(dev, torch.float32)
-                # weight_norm(dim=2): w[:, :, k] = g[k] v[:, :, k] / ||v[:, :, k]||_F -- folded once, the module is frozen
-                w = g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
-                G, Eg = self.groups, self.embed // self.groups
-                self._view(n).copy_(w.view(G, Eg, Eg, self.conv_pos).permute(0, 1, 3, 2))
-            elif n.startswith("wav2vec2.feature_extractor.conv_layers.") and n.endswith(".conv.weight"):
-                self._view(n).copy_(sd[n].to(dev, torch.float32).permute(0, 2, 1))
-            else:
-                self._view(n).copy_(sd[n].to(dev, torch.float32).view(shape))
-        self.invalidate_bf16()
+        self._copy_in(sd)
 
     # -- forward -----------------------------------------------------------------------------------------------------
-    def out_frames(self, n_samples: int) -> int:
-        """``_get_feat_extract_output_lengths``: floor((n - k) / s) + 1 layer by layer (0 when too short)."""
-        n = int(n_samples)
-        for _, k, s in self.conv:
-            n = 0 if n < k else (n - k) // s + 1
-        return n
-
     def forward_padded(self, wave: torch.Tensor, sample_lens: Sequence[int]):
         """wave [B, N] fp32 raw samples (whatever lies behind an utterance's length is ignored), 16 kHz.  Returns
         ``(logits [B, T, vocab], frame_lens list, ids [B, T] int32, counts [B] int32)``, all device tensors but the list:
