@@ -164,6 +164,23 @@ int s2st_softmax_fwd_f32(const float* s, float* p, float* pd, const int32_t* kle
 /* ds = p * (dp' - sum dp' p), dp' = dropmask * dpd */
 int s2st_softmax_bwd_f32(const float* p, const float* dpd, float* ds, int32_t B, int32_t H, int32_t T, int32_t S, int32_t ld, float drop_p, uint64_t seed, void* stream);
 
+/* The same backward for the alignment layer under --use-guided-attention-loss (criterions/t2s_loss.py:131-133 with :50-88;
+ * s2st_loss.py:226-227): the guided term's gradient w.r.t. the probabilities,
+ *   dp'[b][h][t][s] += coef / (n_cells ? *n_cells : 1) * W_b(t, s),  W_b(t, s) = 1 - exp(-(s / src_lens[b] - t / tgt_lens[b])^2 / (2 sigma^2)),
+ * is added on the cells t < tgt_lens[b], s < src_lens[b] (nothing on padded query rows or padded keys) behind the dropout
+ * backward and in front of the softmax Jacobian, inside the same kernel: W is evaluated there, no weight tensor and no
+ * further pass over a [B, H, T, ld] tensor.  Replaces autograd's backward of GuidedAttentionLoss.forward through
+ * attn.mean(heads) into the last decoder layer's encoder_attn softmax.  coef = 0: exactly s2st_softmax_bwd_f32. */
+int s2st_softmax_bwd_guided_f32(const float* p, const float* dpd, float* ds, int32_t B, int32_t H, int32_t T, int32_t S, int32_t ld, float drop_p, uint64_t seed, float coef, float sigma, const float* n_cells, const int32_t* src_lens, const int32_t* tgt_lens, void* stream);
+
+/* GuidedAttentionLoss.forward (criterions/t2s_loss.py:83-88; s2st_loss.py:139-144): attn [B][S][T] is the head-averaged
+ * alignment of the last decoder layer; out[0] = sum over b, t < tgt_lens[b], s < src_lens[b] of W_b(t, s) * attn[b][s][t],
+ * out[1] = the cell count N = sum_b src_lens[b] * tgt_lens[b] (also, exactly, *n_cells when given); the loss is out[0] / out[1].
+ * W is evaluated in the kernel.  scratch: s2st_guided_attn_scratch(B, S) floats of per-workgroup partial sums, folded in
+ * index order by a second kernel -- no float atomics, the value repeats bit for bit. */
+int64_t s2st_guided_attn_scratch(int32_t B, int32_t S);
+int s2st_guided_attn_fwd_f32(const float* attn, const int32_t* src_lens, const int32_t* tgt_lens, int32_t B, int32_t S, int32_t T, float sigma, float* scratch, float* out, int64_t* n_cells, void* stream);
+
 /* bias gradients: out[c] (+)= sum_r x[r][c] */
 int s2st_colsum_f32(const float* x, int64_t ld, int32_t rows, int32_t cols, float* out, int32_t accumulate, void* stream);
 
@@ -350,6 +367,14 @@ typedef struct {
    * tokens: stats[S2ST_STAT_LOSS] = that sum, S2ST_STAT_ASR_NLL / _SMOOTH / _CORRECT / _TOTAL its parts and the accuracy
    * counts; outputs.asr_logits = [B, Ls, tgt_vocab].  No mel decoder, post-net, CTC or aux heads exist in this mode. */
   int32_t s2t_mode;
+  /* --use-guided-attention-loss / --guided-attention-loss-sigma / --attn-loss-weight (criterions/t2s_loss.py:101-103,
+   * 131-133; s2st_loss.py:226-227, 245-257): guided != 0 adds w_attn * mean over the valid cells of W (.) attn to the loss.
+   * The last decoder layer's cross-attention then keeps its probabilities (unfused path) in every forward with a loss,
+   * whether or not the caller asked for the alignment; source-side lengths are the encoder OUTPUT lengths (the batch's
+   * enc_lens: the text lengths for a text encoder, as the reference passes them; the subsampled lengths for speech
+   * input, where the reference itself passes fbank lengths and raises). */
+  int32_t guided;
+  float guided_sigma, w_attn;
 } s2st_model_config;
 
 typedef struct {
@@ -411,7 +436,8 @@ enum {
   S2ST_STAT_ASR_NLL = 3, S2ST_STAT_ASR_SMOOTH = 4, S2ST_STAT_ASR_CORRECT = 5, S2ST_STAT_ASR_TOTAL = 6,
   S2ST_STAT_ST_NLL = 7, S2ST_STAT_ST_SMOOTH = 8, S2ST_STAT_ST_CORRECT = 9, S2ST_STAT_ST_TOTAL = 10,
   S2ST_STAT_LOSS = 16, S2ST_STAT_L1 = 17, S2ST_STAT_MSE = 18, S2ST_STAT_EOS = 19,
-  S2ST_STAT_CTC = 20, S2ST_STAT_ASR = 21, S2ST_STAT_ST = 22, S2ST_STAT_CTC_TGT = 23, S2ST_STAT_GNORM = 24
+  S2ST_STAT_CTC = 20, S2ST_STAT_ASR = 21, S2ST_STAT_ST = 22, S2ST_STAT_CTC_TGT = 23, S2ST_STAT_GNORM = 24,
+  S2ST_STAT_ATTN = 25 /* attn_loss_weight * guided-attention loss (0 with the flag off) */
 };
 
 typedef struct s2st_engine s2st_engine;

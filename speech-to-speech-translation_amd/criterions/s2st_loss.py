@@ -5,6 +5,12 @@ Mirror of examples/s2s_trans/criterions/s2st_loss.py:147-413: same constructor a
 logging keys, ``reduce_metrics`` and ``logging_outputs_can_be_summed() == False``.  The loss
 terms and their gradients are computed by the HIP kernels (mel L1/MSE/BCE, CTC,
 label-smoothed CE); ``loss.backward()`` runs the engine's backward through one autograd node.
+
+``--use-guided-attention-loss`` (s2st_loss.py:106-144, 226-227): the term is computed on the head-averaged alignment of
+the last decoder layer with the encoder OUTPUT lengths on the source side.  For ``t2s_loss`` those are the text lengths
+the reference passes, and the term is pinned against the reference (tests/golden/s2st_tiny_t2s_guided.npz).  For
+``s2st_loss`` and ``s2st_loss_mtl`` it is **parity unpinned: the reference raises there** -- it passes fbank lengths
+against the ``[B, E, D]`` map; the subsampled lengths are the only self-consistent reading, and the one the CPU oracle uses.
 """
 from __future__ import annotations
 
@@ -95,7 +101,7 @@ class LazyLog(dict):
         for k, i in (("loss", "LOSS"), ("l1_loss", "L1"), ("mse_loss", "MSE"), ("eos_loss", "EOS"),
                      ("ctc_loss", "CTC"), ("aux_asr_loss", "ASR"), ("aux_st_loss", "ST")):
             dict.__setitem__(self, k, s[STAT[i]])
-        dict.__setitem__(self, "attn_loss", 0.0)
+        dict.__setitem__(self, "attn_loss", s[STAT["ATTN"]])  # 0.0 without --use-guided-attention-loss
         if self._acc[0]:
             dict.__setitem__(self, "asr_n_correct", int(s[STAT["ASR_CORRECT"]]))
             dict.__setitem__(self, "asr_total", int(s[STAT["ASR_TOTAL"]]))
@@ -133,11 +139,12 @@ class Tacotron2Criterion(CriterionBase):  # fairseq's FairseqCriterion when fair
             super().__init__(task)
         else:
             super().__init__()
-        if use_guided_attention_loss:
-            # the reference raises a shape error with this flag on (fbank lengths are passed to a
-            # [B, E, D] attention map, s2st_loss.py:227); nothing to be compatible with
-            raise NotImplementedError("guided attention loss is unusable in the reference; not built")
         self.task = task
+        # the term and its gradient are the engine's (csrc/losses.hip, rowops.hip); the flags reach it through the model's
+        # config (runtime/engine.py config_from_args) and forward() checks that the two agree
+        self.use_guided_attention_loss = bool(use_guided_attention_loss)
+        self.guided_attention_loss_sigma = guided_attention_loss_sigma
+        self.attn_loss_weight = attn_loss_weight
         self.sentence_avg = sentence_avg
         self.n_frames_per_step = n_frames_per_step
         self.bce_pos_weight = bce_pos_weight
@@ -167,6 +174,9 @@ class Tacotron2Criterion(CriterionBase):  # fairseq's FairseqCriterion when fair
         mine = (self.ctc_weight, self.asr_ce_weight, self.st_ce_weight, self.l1_loss_weight,
                 self.mse_loss_weight, self.eos_loss_weight, self.bce_pos_weight, self.eps)
         assert all(abs(a - b) < 1e-6 for a, b in zip(c_w, mine)), "criterion and model flags disagree"
+        assert bool(c.guided) == self.use_guided_attention_loss and (not c.guided or (
+            abs(c.guided_sigma - self.guided_attention_loss_sigma) < 1e-6 and abs(c.w_attn - self.attn_loss_weight) < 1e-6)), \
+            "criterion and model disagree on --use-guided-attention-loss / its sigma / --attn-loss-weight"
         sample = model.front_end_sample(sample)  # --use-hubert (s2st_transformer.py:245-252)
         out = eng.forward(sample, training=model.training, want_attn=False, with_loss=True)
         self.last_outputs = out

@@ -64,6 +64,14 @@ int s2st_colsum_f32(const float* x, int64_t ld, int32_t rows, int32_t cols, floa
   return s2st_colsum(x, ld, rows, cols, out, accumulate, (hipStream_t)stream);
 }
 
+int s2st_softmax_bwd_guided_f32(const float* p, const float* dpd, float* ds, int32_t B, int32_t H, int32_t T, int32_t S, int32_t ld, float drop_p, uint64_t seed, float coef, float sigma, const float* n_cells, const int32_t* src_lens, const int32_t* tgt_lens, void* stream) {
+  s2st_guided_args ga{coef, (float)(2.0 * (double)sigma * (double)sigma), n_cells, src_lens, tgt_lens};
+  return s2st_softmax_bwd(p, dpd, ds, B, H, T, S, ld, drop_p, seed, (hipStream_t)stream, nullptr, &ga);
+}
+int64_t s2st_guided_attn_scratch(int32_t B, int32_t S) { return s2st_guided_attn_blocks(B, S); }
+int s2st_guided_attn_fwd_f32(const float* attn, const int32_t* src_lens, const int32_t* tgt_lens, int32_t B, int32_t S, int32_t T, float sigma, float* scratch, float* out, int64_t* n_cells, void* stream) {
+  return s2st_guided_attn_fwd(attn, src_lens, tgt_lens, B, S, T, sigma, scratch, out, (long long*)n_cells, (hipStream_t)stream);
+}
 int s2st_attn_headmean_f32(const float* p, float* out, int32_t B, int32_t H, int32_t T, int32_t S, int32_t ld, void* stream) {
   return s2st_attn_headmean(p, out, B, H, T, S, ld, (hipStream_t)stream);
 }

@@ -411,6 +411,8 @@ int s2st_engine_create(const s2st_model_config* cfg, s2st_engine** out) {
     return S2ST_ERR_SHAPE;
   // the two-utterance-half-chain schedule measured neutral and was removed (profiles/r05_chains_ab.txt): asked for and not available is loud
   if (!cfg->precise && s2st_env_int("S2ST_CHAINS", 1) != 1) return S2ST_ERR_ARG;
+  // guided-attention term: a mel decoder's alignment layer and a positive sigma
+  if (cfg->guided && (cfg->s2t_mode || cfg->dec_layers <= 0 || !(cfg->guided_sigma > 0.f))) return S2ST_ERR_ARG;
   s2st_engine* e = new s2st_engine();
   e->c = *cfg;
   e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");

@@ -232,8 +232,11 @@
     Ten* kt; int koff, ldk;
     Ten* vt; int voff, ldv;
   };
+  // guided_sum (with attn_mean_out: the alignment layer under --use-guided-attention-loss): {sum, N} of the guided term
+  // (s2st_guided_attn_fwd) -- the backward adds the term's gradient inside its softmax kernel; klen are then the
+  // source-side lengths of the term
   Ten* attention(const AttnIO& io, int B, int T, int S, int H, int dh, const int* klen, int causal,
-                 float drop_p, float* attn_mean_out /* [B][S][T] or null */) {
+                 float drop_p, float* attn_mean_out /* [B][S][T] or null */, const float* guided_sum = nullptr) {
     const int C = H * dh;
     const int ld = (S + 7) / 8 * 8;
     const bool fm = fast();
@@ -392,7 +395,15 @@
       // dV = Pd^T dO
       bgemm(View{pd, pdh}, 0, ld, pzo, Vdo, 0, C, (long)T * C, gv + io2.voff, io2.ldv, (long)S * io2.ldv, dh, pzi,
             dh, S, dh, T, 1.f);
-      chk(s2st_softmax_bwd(p, dp, dp, B, H, T, S, ld, drop_p, sd, st_, dsh));
+      s2st_guided_args ga{};
+      if (guided_sum) {
+        ga.coef = gscale * c.w_attn / (float)H;
+        ga.two_sig2 = (float)(2.0 * (double)c.guided_sigma * (double)c.guided_sigma);
+        ga.n_cells = guided_sum + 1;
+        ga.src_lens = klen;
+        ga.tgt_lens = bt.tgt_lens;
+      }
+      chk(s2st_softmax_bwd(p, dp, dp, B, H, T, S, ld, drop_p, sd, st_, dsh, guided_sum ? &ga : nullptr));
       // dQ = scaling * dS K ; dK = scaling * dS^T Q
       bgemm(View{dp, dsh}, 1, ld, pzo, Vk, 0, io2.ldk, (long)S * io2.ldk, gq + io2.qoff, io2.ldq,
             (long)T * io2.ldq, dh, pzi, dh, T, dh, S, scaling);
@@ -415,7 +426,8 @@
   }
   // q: the projected queries (dec_head)
   Ten* cross_attn_block(Ten* q, Ten* encx, const XAttnP& a, int B, int T, int S, int H,
-                        const int* klen, Ten* resid, float* attn_mean_out, Ten* kv_pre = nullptr) {
+                        const int* klen, Ten* resid, float* attn_mean_out, Ten* kv_pre = nullptr,
+                        const float* guided_sum = nullptr) {
     const int C = q->cols;
     Ten* kv = kv_pre ? kv_pre : cross_kv(encx, a, C);
     if (kv_pre && kv_wait_) {  // first consumer of the projections issued on the second stream
@@ -423,7 +435,7 @@
       kv_wait_ = false;
     }
     AttnIO io{q, 0, C, kv, 0, 2 * C, kv, C, 2 * C};
-    Ten* o = attention(io, B, T, S, H, C / H, klen, 0, bt.training ? c.attn_dropout : 0.f, attn_mean_out);
+    Ten* o = attention(io, B, T, S, H, C / H, klen, 0, bt.training ? c.attn_dropout : 0.f, attn_mean_out, guided_sum);
     if (kv_pre && !xattn0_idx) xattn0_idx = tape.size() - 1;  // (mel-decoder layer 0: what lies below this closure may leave the data path, backward_segment)
     return linear(o, a.out_w, a.out_b, C, C, 0, bt.training ? c.dropout : 0.f, resid);
   }
@@ -461,9 +473,10 @@
   }
   // head: the layer's dec_head() was issued ahead (x is not read then)
   Ten* dec_layer(Ten* x, Ten* encx, const DecLayerP& l, int B, int T, int S, int H, bool pre_ln,
-                 const int* self_klen, float* attn_mean_out, Ten* kv_pre = nullptr, const DecHead* head = nullptr) {
+                 const int* self_klen, float* attn_mean_out, Ten* kv_pre = nullptr, const DecHead* head = nullptr,
+                 const float* guided_sum = nullptr) {
     const DecHead h = head ? *head : dec_head(x, l, B, T, H, pre_ln, self_klen);
-    x = cross_attn_block(h.q, encx, l.xa, B, T, S, H, bt.enc_lens, h.x, attn_mean_out, kv_pre);
+    x = cross_attn_block(h.q, encx, l.xa, B, T, S, H, bt.enc_lens, h.x, attn_mean_out, kv_pre, guided_sum);
     if (pre_ln) return ffn_block(layernorm(x, l.ln3, nullptr, true), l.fc1, l.fc2, x);
     x = layernorm(x, l.ln2);
     return layernorm(ffn_block(x, l.fc1, l.fc2, x), l.ln3);

@@ -359,12 +359,23 @@
     if (dec_early) file_early(early.n_front, early.tape.size(), early.wm_head);
     float* attn_out = nullptr;
     Ten* tap_dec_t = nullptr;
+    // --use-guided-attention-loss: every forward with a loss needs the alignment layer's map, asked for or not (kept in
+    // the workspace when the caller gave no buffer), and its backward the term's {sum, N}
+    const bool guided = c.guided != 0 && with_loss && c.dec_layers > 0;
+    float* guided_map = nullptr;
+    float* guided_sum = nullptr;
+    if (guided) {
+      guided_map = (bt.want_attn && outs.attn) ? outs.attn : alloc((long)B * E * D);
+      guided_sum = alloc(2);
+    }
     for (int i = 0; i < c.dec_layers; ++i) {
       float* am = (i == c.dec_layers - 1 && bt.want_attn) ? outs.attn : nullptr;
+      const bool align = guided && i == c.dec_layers - 1;
+      if (align) am = guided_map;
       set_ctx("dec.L%d", i);
       if (dec_early && kv_on_side && i == 1) kv_wait_ = true;
       y = dec_layer(y, enc_out, dec[i], B, D, E, c.dec_heads, c.dec_pre_ln != 0, bt.tgt_lens, am, xkv[i],
-                    (dec_early && i == 0) ? &early.head : nullptr);
+                    (dec_early && i == 0) ? &early.head : nullptr, align ? guided_sum : nullptr);
       if (c.has_ctc_tgt && i == c.tap_dec) tap_dec_t = y;  // raw layer output (s2st_transformer_mtl.py:325-327)
       if (i % 2 == 1) mark();
     }
@@ -447,8 +458,13 @@
       float* stats = outs.stats;
       const float nr = (float)bt.ntokens, nf = nr * c.out_dim;
       float* loss_ws = alloc(3L * S2ST_LOSS_ORDERED_FLOATS);
+      float* guided_part = guided ? alloc(s2st_guided_attn_blocks(B, E)) : nullptr;
       if (live()) {
         hipMemsetAsync(stats, 0, sizeof(float) * 32, st_);
+        // guided-attention term: sum of W (.) alignment over the valid cells and their count (fixed-order sums always)
+        if (guided)
+          chk(s2st_guided_attn_fwd(guided_map, bt.enc_lens, bt.tgt_lens, B, E, D, c.guided_sigma, guided_part, guided_sum,
+                                   nullptr, st_));
         // ordered sums: the loss kernels leave per-workgroup sums, the finalize kernel adds them in workgroup order
         s2st_loss_parts lp{};
         float* ow[3] = {nullptr, nullptr, nullptr};
@@ -466,7 +482,7 @@
         chk(s2st_loss_finalize(stats, ctc_per, B, nf, nr, c.w_l1, c.w_mse, c.w_eos, c.ctc_weight,
                                c.asr_weight, c.st_weight, c.label_smoothing, c.src_vocab, c.tgt_vocab,
                                (float)bt.src_txt_ntokens, (float)bt.tgt_txt_ntokens, st_, ctc_tgt_per, c.ctc_tgt_weight,
-                               ordered_sums ? &lp : nullptr));
+                               ordered_sums ? &lp : nullptr, guided ? guided_sum : nullptr, c.w_attn));
       }
       tape.push_back([=]() {
         // roots of the backward: d loss / d {feat, post, eos, logits}

@@ -334,12 +334,55 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   }
 }
 
+// guided-attention term, first pass: one wave per (b, s) row of the head-averaged alignment [B][S][T], lanes over the
+// decoder steps (contiguous); rows s >= src_lens[b] and steps t >= tgt_lens[b] are never read.  The workgroup's sum (four
+// waves, added in wave order) goes to part[blockIdx.x]; the rows a workgroup visits and their order are fixed by the grid.
+__global__ __launch_bounds__(256) void guided_attn_part_kernel(const float* __restrict__ attn, const int* __restrict__ src_lens,
+                                                               const int* __restrict__ tgt_lens, int B, int S, int T,
+                                                               float two_sig2, float* __restrict__ part) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long rows = (long)B * S;
+  float a = 0.f;
+  for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
+    const int b = (int)(row / S), s = (int)(row - (long)b * S);
+    const int sl = src_lens[b], tl = tgt_lens[b];
+    if (s >= sl) continue;
+    const int tn = min(tl, T);
+    const float* ar = attn + row * T;
+    for (int t = lane; t < tn; t += 64) a += guided_w(s, t, (float)sl, (float)tl, two_sig2) * ar[t];
+  }
+  a = wave_sum(a);
+  if (lane == 0) red[wave] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// second pass (one wave): out[0] = the partial sums added in index order (lane-strided, then the fixed wave tree),
+// out[1] = the cell count N = sum_b src_lens[b] * tgt_lens[b], formed in integers
+__global__ __launch_bounds__(64) void guided_attn_fold_kernel(const float* __restrict__ part, int nb,
+                                                              const int* __restrict__ src_lens, const int* __restrict__ tgt_lens,
+                                                              int B, int S, int T, float* __restrict__ out,
+                                                              long long* __restrict__ n_cells) {
+  const int lane = threadIdx.x;
+  float v = 0.f;
+  for (int i = lane; i < nb; i += 64) v += part[i];
+  v = wave_sum(v);
+  if (lane != 0) return;
+  long long n = 0;
+  for (int b = 0; b < B; ++b) n += (long long)max(min(src_lens[b], S), 0) * max(min(tgt_lens[b], T), 0);
+  out[0] = v;
+  out[1] = (float)n;
+  if (n_cells) *n_cells = n;
+}
+
 // stats[16..22] = {loss, l1, mse, eos, ctc, asr, st} from the raw sums (s2st_loss.py:245-257)
 __global__ void loss_finalize_kernel(float* __restrict__ stats, const float* __restrict__ ctc_per, int B,
                                      float nf, float nr, float w_l1, float w_mse, float w_eos,
                                      float w_ctc, float w_asr, float w_st, float eps, int Vs, int Vt,
                                      float src_ntok, float tgt_ntok, const float* __restrict__ ctc_tgt_per,
-                                     float w_ctc_tgt, s2st_loss_parts parts) {
+                                     float w_ctc_tgt, s2st_loss_parts parts, const float* __restrict__ attn_sum,
+                                     float w_attn) {
   if (parts.on) {  // the loss kernels' per-workgroup sums, added in workgroup order (wave-strided, fixed tree)
     const int lane = threadIdx.x & 63;
     for (int o = threadIdx.x >> 6; o < 11; o += blockDim.x >> 6) {
@@ -384,7 +427,13 @@ __global__ void loss_finalize_kernel(float* __restrict__ stats, const float* __r
   stats[S2ST_STAT_ASR] = asr;
   stats[S2ST_STAT_ST] = st;
   stats[S2ST_STAT_CTC_TGT] = ctc_tgt;
-  stats[S2ST_STAT_LOSS] = l1 + mse + eos + ctc + ctc_tgt + asr + st;
+  float loss = l1 + mse + eos + ctc + ctc_tgt + asr + st;
+  if (attn_sum) {  // guided-attention term: the mean over the N valid cells (s2st_guided_attn_fwd), times its weight
+    const float attn = attn_sum[1] > 0.f ? w_attn * (attn_sum[0] / attn_sum[1]) : 0.f;
+    stats[S2ST_STAT_ATTN] = attn;
+    loss += attn;
+  }
+  stats[S2ST_STAT_LOSS] = loss;
 }
 
 // (log-)softmax over the last dimension, one wave per row (models' get_normalized_probs: s2st_transformer.py:458-463,
@@ -468,11 +517,31 @@ int s2st_ctc(const float* logits, const long* targets, int Lmax, const int* in_l
 int s2st_loss_finalize(float* stats, const float* ctc_per, int B, float nf, float nr, float w_l1,
                        float w_mse, float w_eos, float w_ctc, float w_asr, float w_st, float eps, int Vs,
                        int Vt, float src_ntok, float tgt_ntok, hipStream_t st, const float* ctc_tgt_per, float w_ctc_tgt,
-                       const s2st_loss_parts* parts) {
+                       const s2st_loss_parts* parts, const float* attn_sum, float w_attn) {
   s2st_loss_parts pt{};
   if (parts) { pt = *parts; pt.on = 1; }
   S2ST_LAUNCH(loss_finalize_kernel, dim3(1), dim3(parts ? 256 : 64), 0, st, stats, ctc_per, B, nf, nr, w_l1, w_mse,
-                     w_eos, w_ctc, w_asr, w_st, eps, Vs, Vt, src_ntok, tgt_ntok, ctc_tgt_per, w_ctc_tgt, pt);
+                     w_eos, w_ctc, w_asr, w_st, eps, Vs, Vt, src_ntok, tgt_ntok, ctc_tgt_per, w_ctc_tgt, pt, attn_sum, w_attn);
+  return LAUNCH_OK();
+}
+
+int s2st_guided_attn_blocks(int B, int S) {
+  const long rows = (long)B * S;
+  if (rows <= 0) return 0;
+  const long blocks = (rows + 3) / 4;
+  return (int)(blocks > 1024 ? 1024 : blocks);
+}
+
+int s2st_guided_attn_fwd(const float* attn, const int* src_lens, const int* tgt_lens, int B, int S, int T, float sigma,
+                         float* part, float* out, long long* n_cells, hipStream_t st) {
+  if (B < 0 || S < 0 || T < 0 || !(sigma > 0.f) || !out) return S2ST_ERR_ARG;
+  const int nb = (T > 0) ? s2st_guided_attn_blocks(B, S) : 0;
+  if (nb > 0 && (!attn || !src_lens || !tgt_lens || !part)) return S2ST_ERR_ARG;
+  const float two_sig2 = (float)(2.0 * (double)sigma * (double)sigma);
+  if (nb > 0)
+    S2ST_LAUNCH(guided_attn_part_kernel, dim3(nb), dim3(256), 0, st, attn, src_lens, tgt_lens, B, S, T, two_sig2, part);
+  S2ST_LAUNCH(guided_attn_fold_kernel, dim3(1), dim3(64), 0, st, (const float*)part, nb, src_lens, tgt_lens, nb > 0 ? B : 0, S, T,
+              out, n_cells);
   return LAUNCH_OK();
 }
 

@@ -447,17 +447,31 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restric
   }
 }
 
+// GUIDED: the guided-attention term's gradient w.r.t. the probabilities joins the row behind the dropout backward and in
+// front of the Jacobian (s2st_guided_args, s2st_ops.h); row = (b * H + h) * T + t.  <false> is the kernel as it was.
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restrict__ p,
                                                           const float* __restrict__ dpd,
                                                           float* __restrict__ ds, long rows, int S,
                                                           int ld, float drop_p, uint64_t seed,
-                                                          uint16_t* __restrict__ dsh) {
+                                                          uint16_t* __restrict__ dsh, s2st_guided_args ga, int H, int T) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
   float pv[SM_MAXE], dv[SM_MAXE];
   float dot = 0.f;
+  int g_lim = 0;  // GUIDED: keys of this row that carry the term (0 on a padded query row)
+  float g_coef = 0.f, g_sl = 1.f, g_tl = 1.f;
+  int g_t = 0;
+  if (GUIDED) {
+    const int b = (int)(row / ((long)H * T));
+    g_t = (int)(row % T);
+    const int sl = ga.src_lens[b], tl = ga.tgt_lens[b];
+    g_lim = g_t < tl ? min(sl, S) : 0;
+    g_sl = (float)sl; g_tl = (float)tl;
+    g_coef = ga.n_cells ? ga.coef / *ga.n_cells : ga.coef;
+  }
 #pragma unroll
   for (int i = 0; i < SM_MAXE; ++i) {
     int c = lane + 64 * i;
@@ -466,6 +480,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
       pv[i] = p[row * ld + c];
       dv[i] = dpd[row * ld + c];
       if (drop_p > 0.f) dv[i] *= drop_scale(seed, (uint64_t)row * ld + c, drop_p, inv_keep);
+      if (GUIDED && c < g_lim) dv[i] += g_coef * guided_w(c, g_t, g_sl, g_tl, ga.two_sig2);
       dot += pv[i] * dv[i];
     }
   }
@@ -698,12 +713,18 @@ int s2st_softmax_fwd(const float* s, float* p, float* pd, const int* klen, int B
 }
 
 int s2st_softmax_bwd(const float* p, const float* dpd, float* ds, int B, int H, int T, int S,
-                     int ld, float drop_p, uint64_t seed, hipStream_t st, uint16_t* dsh) {
+                     int ld, float drop_p, uint64_t seed, hipStream_t st, uint16_t* dsh, const s2st_guided_args* guided) {
   long rows = (long)B * H * T;
   if (rows <= 0) return 0;
   if (S > SM_MAXE * 64 || ld > SM_MAXE * 64) return S2ST_ERR_SHAPE;
-  S2ST_LAUNCH(softmax_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p,
-                     dpd, ds, rows, S, ld, drop_p, seed, dsh);
+  if (guided && guided->coef != 0.f) {
+    if (!guided->src_lens || !guided->tgt_lens || !(guided->two_sig2 > 0.f)) return S2ST_ERR_ARG;
+    S2ST_LAUNCH(softmax_bwd_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p,
+                       dpd, ds, rows, S, ld, drop_p, seed, dsh, *guided, H, T);
+  } else {
+    S2ST_LAUNCH(softmax_bwd_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p,
+                       dpd, ds, rows, S, ld, drop_p, seed, dsh, s2st_guided_args{}, H, T);
+  }
   return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
 }
 

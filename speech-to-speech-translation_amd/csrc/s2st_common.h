@@ -57,6 +57,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// guided-attention weight of cell (decoder step t, encoder position s) of an utterance with src_len encoder positions and
+// tgt_len decoder steps (criterions/t2s_loss.py:60-67): the ONE place it is evaluated -- the loss kernel and the alignment
+// layer's softmax backward both call it, no weight tensor exists in memory
+__device__ __forceinline__ float guided_w(int s, int t, float src_len, float tgt_len, float two_sig2) {
+  const float d = (float)s / src_len - (float)t / tgt_len;
+  return 1.f - expf(-(d * d) / two_sig2);
+}
+
 // exact GELU (nn.GELU(), fairseq utils.gelu: 0.5 x (1 + erf(x / sqrt 2)))
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 // The same function for the bf16-operand kernels' epilogues (HuBERT's conv stack and FFN: 670 M evaluations per 24 x 8 s

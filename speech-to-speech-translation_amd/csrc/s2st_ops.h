@@ -139,9 +139,21 @@ int s2st_softmax_fwd(const float* s, float* p, float* pd, const int* klen, int B
                      int S, int ld, int causal, float drop_p, uint64_t seed, hipStream_t st,
                      uint16_t* pdh = nullptr /* optional bf16 copy of dropout(p), pad cols zeroed */);
 // ds = p * (dp' - sum(dp' * p)),  dp' = dropmask * dpd ; in place allowed (ds == dpd)
+// guided (optional argument block, the alignment layer under --use-guided-attention-loss): the guided-attention term's
+// gradient joins dp' before the Jacobian -- dp'[b][h][t][s] += coef / (n_cells ? *n_cells : 1) * W_b(t, s) on the cells
+// t < tgt_lens[b], s < src_lens[b], nothing elsewhere; W is evaluated in the kernel (guided_w, s2st_common.h).  Absent,
+// or with coef == 0: the unguided kernel, bit for bit
+struct s2st_guided_args {
+  float coef;            // gs * attn_loss_weight / H
+  float two_sig2;        // 2 sigma^2
+  const float* n_cells;  // device: the term's cell count N (s2st_guided_attn_fwd's out[1]); null: 1
+  const int* src_lens;   // [B] encoder output lengths
+  const int* tgt_lens;   // [B] decoder steps
+};
 int s2st_softmax_bwd(const float* p, const float* dpd, float* ds, int B, int H, int T, int S,
                      int ld, float drop_p, uint64_t seed, hipStream_t st,
-                     uint16_t* dsh = nullptr /* optional bf16 copy of ds, pad cols zeroed */);
+                     uint16_t* dsh = nullptr /* optional bf16 copy of ds, pad cols zeroed */,
+                     const s2st_guided_args* guided = nullptr);
 
 // column sums: out[c] (+)= sum_r x[r][c]   (bias gradients)
 int s2st_colsum(const float* x, long ld, int rows, int cols, float* out, int accumulate,
@@ -457,10 +469,20 @@ int s2st_ctc(const float* logits, const long* targets, int Lmax, const int* in_l
              float* dlogits, float gscale, float* ws, hipStream_t st);
 
 int s2st_log_softmax_rows(const float* x, long ldx, float* y, long ldy, int rows, int V, int log_out, hipStream_t st);
+// guided-attention term (criterions/t2s_loss.py:50-88; s2st_loss.py:106-144): attn [B][S][T] = the head-averaged
+// alignment; out[0] = sum over b, t < tgt_lens[b], s < src_lens[b] of W_b(t, s) * attn[b][s][t],
+// W_b(t, s) = 1 - exp(-(s / src_lens[b] - t / tgt_lens[b])^2 / (2 sigma^2)) evaluated in the kernel; out[1] = the cell
+// count N = sum_b src_lens[b] * tgt_lens[b] (n_cells, optional: the same as an integer).  Per-workgroup partial sums in
+// `part` (s2st_guided_attn_blocks floats) folded in index order by a second one-wave kernel: no atomics, the value repeats
+int s2st_guided_attn_blocks(int B, int S);
+int s2st_guided_attn_fwd(const float* attn, const int* src_lens, const int* tgt_lens, int B, int S, int T, float sigma,
+                         float* part, float* out, long long* n_cells, hipStream_t st);
+// attn_sum (optional): s2st_guided_attn_fwd's out -- stats[S2ST_STAT_ATTN] = w_attn * sum / N joins the total
 int s2st_loss_finalize(float* stats, const float* ctc_per, int B, float nf, float nr, float w_l1,
                        float w_mse, float w_eos, float w_ctc, float w_asr, float w_st, float eps, int Vs,
                        int Vt, float src_ntok, float tgt_ntok, hipStream_t st, const float* ctc_tgt_per = nullptr,
-                       float w_ctc_tgt = 0.f, const s2st_loss_parts* parts = nullptr);
+                       float w_ctc_tgt = 0.f, const s2st_loss_parts* parts = nullptr, const float* attn_sum = nullptr,
+                       float w_attn = 0.f);
 
 // ---------------------------------------------------------------------------------------
 // optimizer (optim.hip)

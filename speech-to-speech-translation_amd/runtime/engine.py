@@ -29,7 +29,7 @@ class ModelConfig(C.Structure):
         "n_speakers", "spk_frozen", "spk_dim")] + [(n, C.c_float) for n in (
         "dropout", "attn_dropout", "act_dropout", "prenet_dropout", "postnet_dropout", "ctc_weight",
         "asr_weight", "st_weight", "w_l1", "w_mse", "w_eos", "bce_pos_weight", "label_smoothing", "ctc_tgt_weight", "enc_dropout")] + \
-        [("s2t_mode", C.c_int32)]
+        [("s2t_mode", C.c_int32), ("guided", C.c_int32), ("guided_sigma", C.c_float), ("w_attn", C.c_float)]
 
 
 class ParamInfo(C.Structure):
@@ -73,7 +73,7 @@ class DecodeReplay(C.Structure):  # s2st_decode_replay (include/s2st_hip.h)
 
 STAT = dict(L1_SUM=0, MSE_SUM=1, BCE_SUM=2, ASR_NLL=3, ASR_SMOOTH=4, ASR_CORRECT=5, ASR_TOTAL=6,
             ST_NLL=7, ST_SMOOTH=8, ST_CORRECT=9, ST_TOTAL=10, LOSS=16, L1=17, MSE=18, EOS=19,
-            CTC=20, ASR=21, ST=22, CTC_TGT=23, GNORM=24)
+            CTC=20, ASR=21, ST=22, CTC_TGT=23, GNORM=24, ATTN=25)
 
 
 def config_from_args(a, precise: bool = False) -> ModelConfig:
@@ -142,6 +142,14 @@ def config_from_args(a, precise: bool = False) -> ModelConfig:
         raise ValueError("s2t_transformer_hubert has no aux heads, CTC heads, text encoder or speaker tables")
     if c.text_input and (c.has_asr or c.has_st or c.has_ctc_tgt or c.enc_conv_k % 2 != 1):
         raise ValueError("t2s_transformer: no aux heads / target-text CTC head; --encoder-conv-kernel-size must be odd")
+    # --use-guided-attention-loss (t2s_loss.py:101-103, 131-133; s2st_loss.py:100, 226-227): t2s_loss has no weight of
+    # (nor s2st_loss_mtl) of its own in the reference: the term enters with 1.0 there
+    c.guided = int(bool(getattr(a, "use_guided_attention_loss", False)))
+    c.guided_sigma = float(getattr(a, "guided_attention_loss_sigma", 0.4))
+    own_weight = getattr(a, "criterion", "s2st_loss") not in ("t2s_loss", "s2st_loss_mtl")  # (s2st_loss.py:100 only)
+    c.w_attn = (float(getattr(a, "attn_loss_weight", 1.0)) if own_weight else 1.0) if c.guided else 0.0
+    if c.guided and (c.s2t_mode or c.dec_layers < 1 or not c.guided_sigma > 0):
+        raise ValueError("--use-guided-attention-loss needs a mel decoder's alignment layer and a positive sigma")
     if c.has_ctc_tgt and not (0 <= c.tap_dec < c.dec_layers):
         raise ValueError("--middle-layers-decoder must name a decoder layer (the reference would index an empty list)")
     return c
