@@ -150,6 +150,15 @@ typedef struct {
 int s2st_flash_attn_fwd_bf16(const s2st_attn_args* args, void* stream);
 /* dO: fp32 [B*T][H*dh]; dvec_scratch: B*H*T floats */
 int s2st_flash_attn_bwd_bf16(const s2st_attn_args* args, const float* dO, float* dvec_scratch, void* stream);
+/* The backward as the training step calls it: the bias gradients leave as per-(block, wave) PARTIAL sums instead of atomic
+ * adds.  db_part: s2st_flash_attn_db_scratch(args) floats holding three arrays of rows [slot][H*dh] -- slots_q rows for dbq,
+ * then slots_k rows for dbk, then slots_k rows for dbv (s2st_flash_attn_db_slots); a projection whose db* pointer is NULL
+ * leaves its rows alone.  Every row of a requested projection is written exactly once with plain stores (rows of waves that
+ * own no query / key hold zeros), dbq / dbk / dbv themselves are NOT written: the caller folds the rows into them in slot
+ * order, which makes the sums repeat bit for bit.  db_part == NULL: the atomic form of s2st_flash_attn_bwd_bf16. */
+int64_t s2st_flash_attn_db_scratch(const s2st_attn_args* args);
+int s2st_flash_attn_db_slots(const s2st_attn_args* args, int32_t* slots_q, int32_t* slots_k);
+int s2st_flash_attn_bwd_parts_bf16(const s2st_attn_args* args, const float* dO, float* dvec_scratch, float* db_part, void* stream);
 
 /* fairseq/modules/layer_norm.py:11-35 (LayerNorm / FusedLayerNorm), forward; saves mean, rstd */
 int s2st_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int32_t rows, int32_t cols, float eps, void* stream);

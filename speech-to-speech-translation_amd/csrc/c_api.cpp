@@ -212,6 +212,18 @@ int s2st_flash_attn_fwd_bf16(const s2st_attn_args* args, void* stream) { return 
 int s2st_flash_attn_bwd_bf16(const s2st_attn_args* args, const float* dO, float* dvec_scratch, void* stream) {
   return s2st_flash_attn_bwd(args, dO, dvec_scratch, (hipStream_t)stream, 0);
 }
+int64_t s2st_flash_attn_db_scratch(const s2st_attn_args* args) { return s2st_flash_attn_db_scratch_floats(args); }
+int s2st_flash_attn_db_slots(const s2st_attn_args* args, int32_t* slots_q, int32_t* slots_k) {
+  if (!args || !slots_q || !slots_k) return S2ST_ERR_ARG;
+  int sq = 0, sk = 0;
+  s2st_flash_attn_db_layout(args, &sq, &sk);
+  *slots_q = sq;
+  *slots_k = sk;
+  return 0;
+}
+int s2st_flash_attn_bwd_parts_bf16(const s2st_attn_args* args, const float* dO, float* dvec_scratch, float* db_part, void* stream) {
+  return s2st_flash_attn_bwd(args, dO, dvec_scratch, (hipStream_t)stream, 0, db_part);
+}
 
 int s2st_argmax_dim1_f32(const float* x, int64_t* idx, int32_t B, int32_t E, int32_t D, void* stream) {
   return s2st_argmax_dim1(x, (long*)idx, B, E, D, (hipStream_t)stream);

@@ -219,45 +219,146 @@ class AttnArgs(C.Structure):
                 ("dbv", C.c_void_p)]
 
 
+DB_SENTINEL = 7.0       # dbq / dbk / dbv under db="parts": the kernels must leave them alone
+BF16_SENTINEL = -1000.0  # exactly representable in bf16; no attention output of unit-scale inputs comes near it
+
+
 def flash_attention(q, k, v, H, *, klen=None, causal=False, scale=None, drop_p=0.0, seed=0, dO=None, bf16_grads=False,
-                    bf16_o=False, scratch=None):
+                    bf16_o=False, scratch=None, layout="dense", pad=0, f32_o=True, f32_grads=True, db=None, ld_drop=None,
+                    override=None, override_bwd=None, full=False):
     """Fused attention on bf16 [B, T, H*dh] / [B, S, H*dh] projections (s2st_flash_attn_*_bf16).
     Returns (o fp32, lse) and, when dO (fp32 [B, T, H*dh]) is given, also (dq, dk, dv) fp32.  ``bf16_o``: the forward also
     leaves the bf16 copy of o (what the engine does); the backward then forms D = rowsum(dO * o) inside its kernels from
-    the bf16 copies instead of running the fp32 row kernel first."""
+    the bf16 copies instead of running the fp32 row kernel first.
+
+    The keyword options after ``scratch`` reproduce the calling conventions of the training step (engine_ops.h):
+
+    * ``layout``: "dense" (three tensors), "self" (q / k / v are column blocks of ONE packed projection [K|V|Q], T == S) or
+      "cross" (dense q, k / v column blocks of a packed [K|V]); the gradients are written in the same layout.  ``pad``:
+      extra columns at the end of every row of those buffers (row stride = columns + pad, a multiple of 8 elements);
+    * ``f32_o`` / ``f32_grads`` = False: no fp32 O / no fp32 gradients are passed (null pointers; needs ``bf16_o`` /
+      ``bf16_grads``);
+    * ``db``: the projections' bias gradients -- "none", "atomic" (+= into three [H*dh] tensors) or "parts"
+      (s2st_flash_attn_bwd_parts_bf16: per-(block, wave) partial rows, the three tensors stay untouched); None = "atomic"
+      with ``bf16_grads`` and "none" without, as before;
+    * ``ld_drop``: row stride of the dropout index space (default: S rounded up to 8);
+    * ``override`` / ``override_bwd``: {field of s2st_attn_args: value or f(args) -> value} applied just before the forward /
+      the backward call ("dO" in ``override_bwd`` replaces that argument), for tests of the launchers' refusals;
+    * ``full`` = True: return a namespace of everything that was passed -- o, oh, lse, dq, dk, dv, dqh, dkh, dvh (views of
+      the packed buffers), dbq, dbk, dbv, db_part with its views dbq_part / dbk_part / dbv_part [slots][H*dh], slots_q,
+      slots_k, the packed buffers themselves (bufs: name -> tensor, data columns first, pad columns last) -- instead of
+      the tuples.  A refused call raises S2STHipError carrying that namespace as ``.outputs``.
+
+    Every output starts from a sentinel, so that a test sees what a call left alone: NaN in the fp32 buffers, ``lse``
+    and the partial-sum scratch, BF16_SENTINEL in the bf16 buffers, DB_SENTINEL in dbq / dbk / dbv under "parts" (zeros
+    under "atomic": the kernels add)."""
+    import types
     require_device(q)
     B, T, Cm = q.shape
     S = k.shape[1]
     dh = Cm // H
+    dev = q.device
+    if db is None:
+        db = "atomic" if bf16_grads else "none"
+    if layout not in ("dense", "self", "cross") or db not in ("none", "atomic", "parts") or pad % 8:
+        raise S2STHipError("flash_attention: unknown layout / db option, or pad not a multiple of 8")
+    if layout == "self" and T != S:
+        raise S2STHipError("flash_attention: the self-packed layout needs T == S")
+    # groups of column blocks that share one buffer (the engine's packed projections), in the engine's order
+    groups = {"dense": (("q",), ("k",), ("v",)), "self": (("k", "v", "q"),), "cross": (("q",), ("k", "v"))}[layout]
+    src = {"q": q, "k": k, "v": v}
+    bufs = {}
+
+    def packed(dtype, fill, tag, data=None):
+        """one buffer per group, [B, rows, n * Cm + pad]; returns the q / k / v column-block views"""
+        views = {}
+        for names in groups:
+            rows = T if names[-1] == "q" else S
+            buf = torch.full((B, rows, len(names) * Cm + pad), fill, dtype=dtype, device=dev)
+            bufs[tag + "".join(names)] = buf
+            for j, nm in enumerate(names):
+                views[nm] = buf[:, :, j * Cm:(j + 1) * Cm]
+                if data is not None:
+                    views[nm].copy_(data[nm])
+        return views
+
+    nan = float("nan")
+    inp = packed(torch.bfloat16, BF16_SENTINEL, "in_", src)
+    ld = {nm: inp[nm].stride(1) for nm in "qkv"}
+
+    def at(view):  # device address of a column-block view
+        return view.data_ptr() if view is not None else None
+
+    r = types.SimpleNamespace(bufs=bufs, slots_q=0, slots_k=0)
     a = AttnArgs()
-    a.q, a.k, a.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
-    a.ldq = a.ldk = a.ldv = Cm
-    o = torch.zeros(B, T, Cm, dtype=torch.float32, device=q.device)
-    lse = torch.zeros(B * H * T, dtype=torch.float32, device=q.device)
-    oh = torch.zeros(B, T, Cm, dtype=torch.bfloat16, device=q.device) if bf16_o else None
-    a.o, a.oh, a.lse, a.klen = o.data_ptr(), ptr(oh), lse.data_ptr(), ptr(klen)
+    a.q, a.k, a.v = at(inp["q"]), at(inp["k"]), at(inp["v"])
+    a.ldq, a.ldk, a.ldv = ld["q"], ld["k"], ld["v"]
+    r.o = torch.full((B, T, Cm), nan, dtype=torch.float32, device=dev) if f32_o else None
+    r.oh = torch.full((B, T, Cm), BF16_SENTINEL, dtype=torch.bfloat16, device=dev) if bf16_o else None
+    lse = torch.full((B * H * T,), nan, dtype=torch.float32, device=dev)
+    r.lse = lse.view(B, H, T)
+    a.o, a.oh, a.lse, a.klen = ptr(r.o), ptr(r.oh), lse.data_ptr(), ptr(klen)
     a.B, a.H, a.T, a.S, a.dh, a.causal = B, H, T, S, dh, 1 if causal else 0
     a.scale = scale if scale is not None else dh ** -0.5
-    a.drop_p, a.seed, a.ld_drop = drop_p, seed, (S + 7) // 8 * 8
-    check(lib().s2st_flash_attn_fwd_bf16(C.byref(a), C.c_void_p(stream_ptr())), "s2st_flash_attn_fwd_bf16")
+    a.drop_p, a.seed, a.ld_drop = drop_p, seed, ld_drop if ld_drop is not None else (S + 7) // 8 * 8
+
+    def apply(ov):
+        extra = {}
+        for key, val in (ov or {}).items():
+            val = val(a) if callable(val) else val
+            if key == "dO":
+                extra[key] = val
+            else:
+                setattr(a, key, val)
+        return extra
+
+    def run(fn, what, *args):
+        try:
+            check(fn(C.byref(a), *args, C.c_void_p(stream_ptr())), what)
+        except S2STHipError as e:
+            e.outputs = r
+            raise
+
+    apply(override)
+    run(lib().s2st_flash_attn_fwd_bf16, "s2st_flash_attn_fwd_bf16")
     if dO is None:
-        return o, lse.view(B, H, T)
+        return r if full else (r.o, r.lse)
     doh = dO.to(torch.bfloat16).contiguous()
-    dq, dk, dv = (torch.zeros_like(x, dtype=torch.float32) for x in (q, k, v))
     if scratch is None:  # (tools/attn_stamp.py passes a larger one: the private stamp build writes clock stamps there)
-        scratch = torch.zeros(B * H * T, dtype=torch.float32, device=q.device)
-    a.doh, a.dq, a.dk, a.dv = doh.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-    extra = None
+        scratch = torch.zeros(B * H * T, dtype=torch.float32, device=dev)
+    a.doh = doh.data_ptr()
+    g32 = packed(torch.float32, nan, "g32_") if f32_grads else {"q": None, "k": None, "v": None}
+    g16 = packed(torch.bfloat16, BF16_SENTINEL, "g16_") if bf16_grads else {"q": None, "k": None, "v": None}
+    r.dq, r.dk, r.dv = g32["q"], g32["k"], g32["v"]
+    r.dqh, r.dkh, r.dvh = g16["q"], g16["k"], g16["v"]
+    a.dq, a.dk, a.dv = at(r.dq), at(r.dk), at(r.dv)
+    a.dqh, a.dkh, a.dvh = at(r.dqh), at(r.dkh), at(r.dvh)
+    r.dbq = r.dbk = r.dbv = r.db_part = r.dbq_part = r.dbk_part = r.dbv_part = None
+    if db != "none":
+        r.dbq, r.dbk, r.dbv = (torch.full((Cm,), DB_SENTINEL if db == "parts" else 0.0, dtype=torch.float32, device=dev)
+                               for _ in range(3))
+        a.dbq, a.dbk, a.dbv = r.dbq.data_ptr(), r.dbk.data_ptr(), r.dbv.data_ptr()
+    dO_arg = apply(override_bwd).get("dO", dO)
+    if db == "parts":
+        sq, sk = C.c_int32(0), C.c_int32(0)
+        check(lib().s2st_flash_attn_db_slots(C.byref(a), C.byref(sq), C.byref(sk)), "s2st_flash_attn_db_slots")
+        r.slots_q, r.slots_k = sq.value, sk.value
+        n = lib().s2st_flash_attn_db_scratch(C.byref(a))
+        if n != (r.slots_q + 2 * r.slots_k) * Cm:
+            raise S2STHipError("s2st_flash_attn_db_scratch disagrees with s2st_flash_attn_db_slots")
+        r.db_part = torch.full((n,), nan, dtype=torch.float32, device=dev)
+        rows = r.db_part.view(-1, Cm)
+        r.dbq_part, r.dbk_part, r.dbv_part = (rows[:r.slots_q], rows[r.slots_q:r.slots_q + r.slots_k],
+                                              rows[r.slots_q + r.slots_k:])
+        run(lib().s2st_flash_attn_bwd_parts_bf16, "s2st_flash_attn_bwd_parts_bf16", ptr(dO_arg), scratch.data_ptr(),
+            r.db_part.data_ptr())
+    else:
+        run(lib().s2st_flash_attn_bwd_bf16, "s2st_flash_attn_bwd_bf16", ptr(dO_arg), scratch.data_ptr())
+    if full:
+        return r
     if bf16_grads:  # also the bf16 copies + bias-gradient column sums
-        extra = [torch.zeros_like(x, dtype=torch.bfloat16) for x in (q, k, v)] + \
-                [torch.zeros(Cm, dtype=torch.float32, device=q.device) for _ in range(3)]
-        a.dqh, a.dkh, a.dvh = (t.data_ptr() for t in extra[:3])
-        a.dbq, a.dbk, a.dbv = (t.data_ptr() for t in extra[3:])
-    check(lib().s2st_flash_attn_bwd_bf16(C.byref(a), dO.data_ptr(), scratch.data_ptr(), C.c_void_p(stream_ptr())),
-          "s2st_flash_attn_bwd_bf16")
-    if extra is not None:
-        return o, lse.view(B, H, T), dq, dk, dv, extra
-    return o, lse.view(B, H, T), dq, dk, dv
+        return r.o, r.lse, r.dq, r.dk, r.dv, [r.dqh, r.dkh, r.dvh, r.dbq, r.dbk, r.dbv]
+    return r.o, r.lse, r.dq, r.dk, r.dv
 
 
 # ---------------------------------------------------------------------------------------------
