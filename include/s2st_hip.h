@@ -677,10 +677,21 @@ int s2st_gl_istft_ola_f32(const float* X, const int32_t* tl, const float* win, c
  * s2st_feature_moments_f32: moments [U][2][n_bins] = column sums and column sums of squares of each utterance's rows, rows
  * folded in a fixed order (n_bins <= 256). */
 int s2st_fbank_kaldi_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* banks, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t size, int32_t shift, int32_t padded, int32_t n_bins, float eps, int64_t n_pairs, int64_t out_rows, void* stream);
+/* s2st_fbank_kaldi_batch_f32: the same filter bank written as the speech encoder's input, for inference from audio files
+ * (translate.py): batch [U][Tmax][n_bins], frame t < T_u of utterance u = (fbank - mean[b]) / std[b] -- an fp32 subtract, then
+ * an IEEE fp32 divide: the bits of _GlobalCMVN.__call__ (fairseq/data/audio/feature_transforms/global_cmvn.py:26-28) on the
+ * packed route's rows -- and frames T_u <= t < Tmax = +0.0 (_collate_frames, speech_to_text_dataset.py:97-116).  Every element
+ * of batch is written by the call (no memset by the caller, no atomics).  Replaces get_features_or_waveform + the source
+ * transform + the collater's padding + the upload (examples/s2s_trans/data/s2st_dataset.py:326-380). */
+int s2st_fbank_kaldi_batch_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* banks, const int32_t* range, const float* mean, const float* std, float* batch, int32_t* offsets, int32_t U, int32_t Lmax, int32_t Tmax, int32_t size, int32_t shift, int32_t padded, int32_t n_bins, float eps, int64_t n_pairs, void* stream);
 int s2st_logmel_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* mel, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int32_t n_mels, float eps, int64_t n_pairs, int64_t out_rows, void* stream);
 int s2st_logmel_frame_split_f32(const float* wave, const int32_t* len, void* As, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int64_t rows, void* stream);
 int s2st_logmel_from_stft_f32(const float* Y, const float* mel, const int32_t* range, float* out, int64_t rows, int32_t F, int32_t Fp, int32_t n_mels, float eps, void* stream);
 int s2st_feature_moments_f32(const float* feats, const int32_t* offsets, float* moments, int32_t U, int32_t n_bins, void* stream);
+/* wave [B][N] fp32 with len[b] valid samples -> pcm [B][N] int16: clip to [-1, 1 - 1/32768], * 32768, round half to even; zeros
+ * behind len[b] (B <= 65535).  Replaces the host arithmetic in front of soundfile.write
+ * (examples/s2s_trans/generate_waveform.py:116-124: PCM_16 is the wav default), so that one int16 copy leaves the device. */
+int s2st_wave_to_pcm16(const float* wave, const int32_t* len, int16_t* pcm, int32_t B, int32_t N, void* stream);
 
 /* AR decoding (speech_generator_for_s2st.py:76-110: one decoder step for the B utterances of a batch): skinny
  * y[M][N] = f(x[M][K] W[N][K]^T + bias) (+ resid), M <= 16, K % 32 == 0; x fp32 (rounded to bf16 in registers like the

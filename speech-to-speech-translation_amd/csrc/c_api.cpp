@@ -386,6 +386,9 @@ int s2st_resample_sinc_f32(const float* x, const int32_t* n_in, const float* tab
 int s2st_fbank_kaldi_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* banks, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t size, int32_t shift, int32_t padded, int32_t n_bins, float eps, int64_t n_pairs, int64_t out_rows, void* stream) {
   return s2st_fbank_kaldi(wave, len, window, tw, banks, range, out, offsets, U, Lmax, size, shift, padded, n_bins, eps, n_pairs, out_rows, (hipStream_t)stream);
 }
+int s2st_fbank_kaldi_batch_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* banks, const int32_t* range, const float* mean, const float* std, float* batch, int32_t* offsets, int32_t U, int32_t Lmax, int32_t Tmax, int32_t size, int32_t shift, int32_t padded, int32_t n_bins, float eps, int64_t n_pairs, void* stream) {
+  return s2st_fbank_kaldi_batch(wave, len, window, tw, banks, range, mean, std, batch, offsets, U, Lmax, Tmax, size, shift, padded, n_bins, eps, n_pairs, (hipStream_t)stream);
+}
 int s2st_logmel_f32(const float* wave, const int32_t* len, const float* window, const float* tw, const float* mel, const int32_t* range, float* out, int32_t* offsets, int32_t U, int32_t Lmax, int32_t n_fft, int32_t hop, int32_t n_mels, float eps, int64_t n_pairs, int64_t out_rows, void* stream) {
   return s2st_logmel(wave, len, window, tw, mel, range, out, offsets, U, Lmax, n_fft, hop, n_mels, eps, n_pairs, out_rows, (hipStream_t)stream);
 }
@@ -397,6 +400,9 @@ int s2st_logmel_from_stft_f32(const float* Y, const float* mel, const int32_t* r
 }
 int s2st_feature_moments_f32(const float* feats, const int32_t* offsets, float* moments, int32_t U, int32_t n_bins, void* stream) {
   return s2st_feature_moments(feats, offsets, moments, U, n_bins, (hipStream_t)stream);
+}
+int s2st_wave_to_pcm16(const float* wave, const int32_t* len, int16_t* pcm, int32_t B, int32_t N, void* stream) {
+  return s2st_wave_pcm16(wave, len, pcm, B, N, (hipStream_t)stream);
 }
 #ifndef S2ST_SOURCE_HASH
 #define S2ST_SOURCE_HASH "unknown"  // (__graft_entry__.build passes the hash of the sources; the test emulator build does not)

@@ -12,6 +12,8 @@
 // odd last frame of an utterance is paired with zeros, never with another utterance's frame: the rounding of a packed
 // transform depends on both halves, and a frame's result must not depend on what else is in the batch.
 // No float atomics; every sum runs in a fixed order.
+// For inference from audio files (translate.py) the filter bank also comes as the encoder's input itself: padded
+// [U][Tmax][n_bins], global CMVN applied (s2st_fbank_kaldi_batch), and generated waveforms leave as 16-bit PCM (s2st_wave_pcm16).
 #include "s2st_ops.h"
 #include "s2st_prof.h"
 #include "fft_lds.h"
@@ -79,12 +81,17 @@ __device__ __forceinline__ int feat_find(const int* __restrict__ off, int U, int
 //          window[size], zero padding to N.
 //   else : frames of N samples every `hop` around the reflect-padded waveform (pad N / 2), window[N].
 // mel [n_bins][N / 2 + 1] dense rows; range[b] = {first bin, one past the last bin} of row b: summed in index order.
-template <int N, bool KALDI>
+// BATCH: the epilogue writes the encoder's input instead of packed rows -- frame t of utterance u at row u * Tmax + t of
+// out [U][Tmax][n_bins], as (value - cmean[b]) / cstd[b] (an fp32 subtract, then an IEEE fp32 divide: _GlobalCMVN's two numpy
+// operations); same pairs, same sums, so `value` has the packed route's bits.  Rows T_u .. Tmax: feat_pad_rows_kernel.
+template <int N, bool KALDI, bool BATCH = false>
 __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__ wave, const int* __restrict__ len,
                                                        const float* __restrict__ win, const cplx* __restrict__ twg,
                                                        const float* __restrict__ mel, const int* __restrict__ range,
                                                        float* __restrict__ out, const int* __restrict__ offs, int U, int Lmax,
-                                                       int size, int hop, int n_bins, float eps, long out_rows) {
+                                                       int size, int hop, int n_bins, float eps, long out_rows,
+                                                       const float* __restrict__ cmean, const float* __restrict__ cstd,
+                                                       int Tmax) {
   __shared__ cplx buf[FftLds<N>::SIZE];
   __shared__ cplx tw[FftLds<N>::SIZE];
   __shared__ float sp[2][N / 2 + 1];
@@ -106,8 +113,8 @@ __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__
   for (int pair = blockIdx.x; pair < npairs; pair += gridDim.x) {
     const int u = feat_find(poff, U, pair);
     const int t0 = 2 * (pair - poff[u]), T = foff[u + 1] - foff[u], L = len[u];
-    const long row0 = (long)foff[u] + t0;
-    const bool on[2] = {row0 < out_rows, t0 + 1 < T && row0 + 1 < out_rows};
+    const long row0 = BATCH ? (long)u * Tmax + t0 : (long)foff[u] + t0;
+    const bool on[2] = {BATCH ? t0 < Tmax : row0 < out_rows, t0 + 1 < T && (BATCH ? t0 + 1 < Tmax : row0 + 1 < out_rows)};
     const float* w = wave + (long)u * Lmax;
     cplx x[PN];
     if (KALDI) {
@@ -176,7 +183,8 @@ __global__ __launch_bounds__(256) void feat_fft_kernel(const float* __restrict__
       const float* m = mel + (long)b * F;
       float acc = 0.f;
       for (int k = range[2 * b]; k < range[2 * b + 1]; ++k) acc += sp[h][k] * m[k];
-      out[(row0 + h) * n_bins + b] = acc > eps ? logf(acc) : log_eps;
+      const float v = acc > eps ? logf(acc) : log_eps;
+      out[(row0 + h) * n_bins + b] = BATCH ? (v - cmean[b]) / cstd[b] : v;
     }
     // (the next pair writes buf / red / sp only behind barriers every thread passes after these reads)
     __syncthreads();
@@ -269,16 +277,48 @@ __global__ __launch_bounds__(256) void feat_moments_kernel(const float* __restri
   }
 }
 
-template <int N, bool KALDI>
+// out [U][Tmax][n_bins]: +0.0 in the rows T_u .. Tmax of every utterance (what _collate_frames pads with); with the BATCH
+// epilogue above, which writes rows 0 .. T_u, every element of `out` is written exactly once
+__global__ __launch_bounds__(256) void feat_pad_rows_kernel(const int* __restrict__ len, float* __restrict__ out, int U, int Tmax,
+                                                            int size, int hop, int n_bins) {
+  for (int u = blockIdx.y; u < U; u += gridDim.y) {
+    const int T = min(feat_frames(len[u], true, size, hop), Tmax);
+    float* o = out + (long)u * Tmax * n_bins;
+    const long end = (long)Tmax * n_bins;
+    for (long i = (long)T * n_bins + blockIdx.x * 256 + threadIdx.x; i < end; i += (long)gridDim.x * 256) o[i] = 0.f;
+  }
+}
+
+// pcm[b][i] = round-half-even(clip(wave[b][i], -1, 1 - 2^-15) * 2^15) for i < len[b], 0 behind it.  The product by 2^15 is
+// exact in fp32, so these are the integers generate_waveform.write_wav forms in float64.
+__global__ __launch_bounds__(256) void wave_to_pcm16_kernel(const float* __restrict__ wave, const int* __restrict__ len,
+                                                            int16_t* __restrict__ pcm, int B, int N) {
+  const int b = blockIdx.y;
+  const int L = min(len[b], N);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+    const long at = (long)b * N + i;
+    float v = 0.f;
+    if (i < L) v = rintf(fminf(fmaxf(wave[at], -1.f), 1.f - 1.f / 32768.f) * 32768.f);
+    pcm[at] = (int16_t)(int)v;
+  }
+}
+
+template <int N, bool KALDI, bool BATCH = false>
 int feat_fft_launch(const float* wave, const int* len, const float* win, const float* tw, const float* mel, const int* range,
                     float* out, int* offs, int U, int Lmax, int size, int hop, int n_bins, float eps, long n_pairs, long out_rows,
-                    hipStream_t st) {
+                    hipStream_t st, const float* cmean = nullptr, const float* cstd = nullptr, int Tmax = 0) {
   S2ST_LAUNCH(feat_offsets_kernel, dim3(1), dim3(256), 0, st, len, offs, U, KALDI ? 1 : 0, KALDI ? size : N, hop);
   if (n_pairs > 0) {
     // (a workgroup keeps its twiddle table and window over the pairs it walks: 8 workgroups per CU at most)
     const unsigned grid = (unsigned)(n_pairs < 2048 ? n_pairs : 2048);
-    S2ST_LAUNCH((feat_fft_kernel<N, KALDI>), dim3(grid), dim3(256), 0, st, wave, len, win, reinterpret_cast<const cplx*>(tw), mel,
-                range, out, offs, U, Lmax, size, hop, n_bins, eps, out_rows);
+    S2ST_LAUNCH((feat_fft_kernel<N, KALDI, BATCH>), dim3(grid), dim3(256), 0, st, wave, len, win,
+                reinterpret_cast<const cplx*>(tw), mel, range, out, offs, U, Lmax, size, hop, n_bins, eps, out_rows, cmean, cstd,
+                Tmax);
+  }
+  if (BATCH) {
+    const long per = (long)Tmax * n_bins;
+    S2ST_LAUNCH(feat_pad_rows_kernel, dim3((unsigned)(per < 64 * 256 ? (per + 255) / 256 : 64), (unsigned)(U < 1024 ? U : 1024)),
+                dim3(256), 0, st, len, out, U, Tmax, size, hop, n_bins);
   }
   return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
 }
@@ -293,6 +333,18 @@ int s2st_fbank_kaldi(const float* wave, const int* len, const float* win, const 
 #define S2ST_FFT_CASE(N) \
   case N: return feat_fft_launch<N, true>(wave, len, win, tw, banks, range, out, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, out_rows, st);
   switch (padded) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) }  // (Kaldi pads its frames to a power of two)
+#undef S2ST_FFT_CASE
+  return S2ST_ERR_SHAPE;
+}
+
+int s2st_fbank_kaldi_batch(const float* wave, const int* len, const float* win, const float* tw, const float* banks,
+                           const int* range, const float* mean, const float* std, float* batch, int* offs, int U, int Lmax, int Tmax,
+                           int size, int shift, int padded, int n_bins, float eps, long n_pairs, hipStream_t st) {
+  if (U <= 0 || Tmax == 0) return 0;
+  if (size < 2 || size > padded || shift < 1 || n_bins < 1 || Lmax < 1 || Tmax < 0) return S2ST_ERR_SHAPE;
+#define S2ST_FFT_CASE(N) \
+  case N: return feat_fft_launch<N, true, true>(wave, len, win, tw, banks, range, batch, offs, U, Lmax, size, shift, n_bins, eps, n_pairs, 0, st, mean, std, Tmax);
+  switch (padded) { S2ST_FFT_POW2_SIZES(S2ST_FFT_CASE) }
 #undef S2ST_FFT_CASE
   return S2ST_ERR_SHAPE;
 }
@@ -334,5 +386,13 @@ int s2st_feature_moments(const float* feats, const int* offs, float* mom, int U,
   if (U <= 0) return 0;
   if (n_bins < 1 || n_bins > 256) return S2ST_ERR_SHAPE;
   S2ST_LAUNCH(feat_moments_kernel, dim3(U), dim3(256), 0, st, feats, offs, mom, n_bins);
+  return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
+}
+
+int s2st_wave_pcm16(const float* wave, const int* len, int16_t* pcm, int B, int N, hipStream_t st) {
+  if (B <= 0 || N == 0) return 0;
+  if (N < 0 || B > 65535) return S2ST_ERR_SHAPE;
+  S2ST_LAUNCH(wave_to_pcm16_kernel, dim3((unsigned)(N < 1024 * 256 ? (N + 255) / 256 : 1024), (unsigned)B), dim3(256), 0, st, wave,
+              len, pcm, B, N);
   return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
 }

@@ -340,6 +340,10 @@ int s2st_resample_sinc(const float* x, const int* n_in, const float* table, floa
 int s2st_fbank_kaldi(const float* wave, const int* len, const float* win, const float* tw, const float* banks, const int* range,
                      float* out, int* offs, int U, int Lmax, int size, int shift, int padded, int n_bins, float eps, long n_pairs,
                      long out_rows, hipStream_t st);
+// the same filter bank as the encoder's input: batch [U][Tmax][n_bins] = (fbank - mean) / std in rows 0 .. T_u, +0.0 behind
+int s2st_fbank_kaldi_batch(const float* wave, const int* len, const float* win, const float* tw, const float* banks,
+                           const int* range, const float* mean, const float* std, float* batch, int* offs, int U, int Lmax, int Tmax,
+                           int size, int shift, int padded, int n_bins, float eps, long n_pairs, hipStream_t st);
 int s2st_logmel(const float* wave, const int* len, const float* win, const float* tw, const float* mel, const int* range,
                 float* out, int* offs, int U, int Lmax, int n_fft, int hop, int n_mels, float eps, long n_pairs, long out_rows,
                 hipStream_t st);
@@ -348,6 +352,8 @@ int s2st_logmel_frame_split(const float* wave, const int* len, uint16_t* As, int
 int s2st_logmel_from_stft(const float* Y, const float* mel, const int* range, float* out, long rows, int F, int Fp, int n_mels,
                           float eps, hipStream_t st);
 int s2st_feature_moments(const float* feats, const int* offs, float* mom, int U, int n_bins, hipStream_t st);
+// wave [B][N] in [-1, 1] -> 16-bit PCM [B][N] (clip, * 2^15, round half to even), zeros behind len[b]
+int s2st_wave_pcm16(const float* wave, const int* len, int16_t* pcm, int B, int N, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh

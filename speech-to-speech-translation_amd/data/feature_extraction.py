@@ -103,7 +103,8 @@ def global_cmvn(moments: np.ndarray, n_frames: int) -> Tuple[np.ndarray, np.ndar
 class DeviceFeatureExtractor:
     """``fbank`` / ``logmel`` of lists of 1-D waveforms on ``device``.  Utterances are taken in order into batches of at most
     ``max_samples`` padded samples (U x longest); a batch is one upload, the kernels, and ONE copy back (features and moments
-    in one buffer).  A frame's bits do not depend on the batch it was extracted in.
+    in one buffer).  A frame's bits do not depend on the batch it was extracted in.  ``fbank_batch`` is the inference form:
+    the normalised, padded encoder input of a batch, left on the device.
 
     ``fft``: the log-mel spectrogram goes through the LDS FFT kernel where the library has a plan for n_fft (256 ... 2048 and
     240 / 400 / 1200, the stage's default); ``False`` forces the dense bf16x3 product that every other n_fft takes (A/B runs)."""
@@ -223,6 +224,69 @@ class DeviceFeatureExtractor:
                     FBANK_EPS, pairs, rows)
 
         return self._run(waves, lambda n: 0 if n < size else 1 + (n - size) // shift, n_bins, launch)
+
+    def fbank_batch(self, waves, sample_rate, mean, std, n_bins: int = 80, Tmax=None, out=None):
+        """The filter bank of a ragged batch as the speech encoder's input (``s2st_fbank_kaldi_batch_f32``): returns
+        ``(src [U, Tmax, n_bins] fp32, frames [U] int64)``, both on the device.  Row ``t < frames[u]`` of utterance ``u`` is
+        ``(fbank - mean) / std`` with the bits ``_GlobalCMVN.__call__`` gives on ``fbank()``'s rows, the rows behind are +0.0
+        as ``_collate_frames`` pads them; the kernel writes every element of ``src``.  ``mean`` / ``std``: [n_bins] fp32
+        (device tensors are used as they are).  ``Tmax`` (default: the longest utterance's frames) may ask for more
+        padding; ``out`` may supply the output tensor.
+
+        ``waves``: 1-D arrays in the 16-bit range, all ``int16`` (uploaded as int16 and widened on the device:
+        ``float(int16)`` is exactly the stage-3 value ``(x / 32768) * 2**15``), or float32 -- or 1-D fp32 tensors already
+        on the device (resampled audio), which are not uploaded at all.  One upload carries the samples and the lengths;
+        nothing comes back to the host."""
+        shift, size, padded, win, tw, banks, rng = self._fbank_tables(sample_rate, n_bins)
+        dev = self.device
+        U = len(waves)
+        lens = [int(w.shape[0]) for w in waves]
+        for w in waves:
+            if len(w.shape) != 1:
+                raise ValueError("feature extraction takes 1-D waveforms (channel 0 / mono)")
+        Ts = [0 if n < size else 1 + (n - size) // shift for n in lens]
+        T = max(Ts, default=0)
+        if Tmax is None:
+            Tmax = T
+        if Tmax < T:
+            raise ValueError(f"fbank_batch: Tmax {Tmax} is smaller than the longest utterance's {T} frames")
+        Lmax = max(max(lens, default=0), 1)
+        hdr = np.asarray(lens, dtype=np.int32)
+        if U and all(torch.is_tensor(w) for w in waves):
+            ln = torch.from_numpy(hdr).to(dev)
+            wave = torch.zeros(U, Lmax, dtype=torch.float32, device=dev)
+            for u, w in enumerate(waves):
+                wave[u, :lens[u]] = w.to(dev, torch.float32)
+        else:
+            # ONE host buffer: the lengths (int32, bit-cast to the samples' type), then the padded samples
+            dt = np.int16 if U and all(isinstance(w, np.ndarray) and w.dtype == np.int16 for w in waves) else np.float32
+            h = hdr.view(dt)
+            host = np.zeros(h.size + U * Lmax, dt)
+            host[:h.size] = h
+            rows = host[h.size:].reshape(U, Lmax)
+            for u, w in enumerate(waves):
+                rows[u, :lens[u]] = np.asarray(w, dtype=dt)
+            d = torch.from_numpy(host).to(dev)
+            ln = d[:h.size].view(torch.int32)
+            wave = d[h.size:].view(U, Lmax).to(torch.float32)  # (int16: widened on the device)
+        mean, std = (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) for x in (mean, std))
+        mean, std = mean.to(dev, torch.float32).contiguous(), std.to(dev, torch.float32).contiguous()
+        if mean.numel() != n_bins or std.numel() != n_bins:
+            raise ValueError(f"fbank_batch: mean / std must hold {n_bins} values")
+        if out is None:
+            out = torch.empty(U, Tmax, n_bins, dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != (U, Tmax, n_bins) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"fbank_batch: out must be a contiguous fp32 tensor of shape {(U, Tmax, n_bins)}")
+        if U:
+            bd.require_device(wave)
+            offs = torch.empty(2, U + 1, dtype=torch.int32, device=dev)
+            bd.call("s2st_fbank_kaldi_batch_f32", wave, ln, win, tw, banks, rng, mean, std, out, offs, U, Lmax, Tmax, size, shift,
+                    padded, n_bins, FBANK_EPS, sum((t + 1) // 2 for t in Ts))
+            n = ln.to(torch.int64)
+            frames = torch.where(n < size, torch.zeros_like(n), 1 + torch.div(n - size, shift, rounding_mode="floor"))
+        else:
+            frames = torch.zeros(0, dtype=torch.int64, device=dev)
+        return out, frames
 
     def logmel(self, waves, sample_rate, n_fft, win_length, hop_length, n_mels, f_min, f_max, eps: float = 1e-5):
         """Waveforms in [-1, 1] -> ([1 + N_u // hop, n_mels] float32 per utterance, moments [U][2][n_mels])."""

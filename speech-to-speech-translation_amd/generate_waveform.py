@@ -132,11 +132,11 @@ def dump_result(args, vocoder_name: str, sample_rate: int, sample_id, hypo, writ
                  lambda p: write_wav(p, _to_np(hypo["targ_waveform"]), sample_rate))
 
 
-def load_task_model_dataset(args, device, configure=None, on_model_built=None):
+def load_task_model(args, device, configure=None, on_model_built=None):
     """What the generation scripts share (generate_waveform.py:134-147, fairseq_cli/generate_for_s2st.py:83-114): the
     checkpoint in the reference's ``.pt`` layout, the task set up from the command line with the checkpoint's model flags
-    (``configure(margs)`` applies the script's own generation-time flags), the model with the checkpoint's tensors, the
-    split.  Returns (task, model, margs, dataset)."""
+    (``configure(margs)`` applies the script's own generation-time flags), the model with the checkpoint's tensors.
+    Returns (task, model, margs)."""
     from . import criterions, models, tasks  # noqa: F401  (fill the registries)
     state = checkpoint_utils.load_checkpoint_to_cpu(args.path)
     margs = state["cfg"]["model"]
@@ -158,6 +158,12 @@ def load_task_model_dataset(args, device, configure=None, on_model_built=None):
     model.load_state_dict(state["model"], strict=True)
     if on_model_built is not None:
         on_model_built(model)
+    return task, model, margs
+
+
+def load_task_model_dataset(args, device, configure=None, on_model_built=None):
+    """``load_task_model`` and the split ``--gen-subset``.  Returns (task, model, margs, dataset)."""
+    task, model, margs = load_task_model(args, device, configure, on_model_built)
     dataset = task.load_dataset(args.gen_subset)
     return task, model, margs, dataset
 

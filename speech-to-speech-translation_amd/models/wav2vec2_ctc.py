@@ -165,7 +165,8 @@ def resample(waves: Sequence[torch.Tensor], sr_from: int, sr_to: int, device=Non
     n_in = [int(w.numel()) for w in waves]
     n_out = [-(-n * L // M) for n in n_in]
     B, Ni, No = len(waves), max(max(n_in), 1), max(max(n_out), 1)
-    x = torch.zeros(B, Ni, dtype=torch.float32)
+    # (waveforms that are already on the device -- translate.py's generated audio -- are gathered there, not on the host)
+    x = torch.zeros(B, Ni, dtype=torch.float32, device=device if all(w.device == device for w in waves) else None)
     for b, w in enumerate(waves):
         x[b, :n_in[b]] = w
     x = x.to(device)

@@ -1,0 +1,482 @@
+"""``translate``: audio files in, translated audio files (and text) out.
+
+    python -m s2st_amd.translate DATA --config-yaml config.yaml --path CKPT.pt --results-path OUT \
+        (--inputs A.wav B.wav ... | --manifest FILE.tsv) [--src-sample-rate R] [--output-sample-rate R] [--speaker NAME] \
+        [--text none|asr|st|both] [--beam 5] [--max-tokens N | --batch-size N] [--vocoder griffin_lim|hifigan] ...
+
+The reference has no such script: its ``generate_waveform.py`` walks a split of a stage-3 data directory (features read
+from a zip through a TSV manifest).  This one joins the pieces that exist into a device-resident path for NEW recordings:
+
+    read_waveform -> (resample on the device) -> s2st_fbank_kaldi_batch_f32: filter bank, global CMVN and padding, written as
+    the encoder's input -> AR decode + vocoder (``task.build_generator_tts``, driven as ``generate_waveform`` drives it) ->
+    (resample on the device) -> s2st_wave_to_pcm16 -> one int16 copy to the host -> ``OUT/wav_<rate>hz_<vocoder>/<id>.wav``
+
+and, with ``--text``, the aux ASR / ST head's beam search (``task.build_generator``, search on the device) into ``OUT/asr.txt``
+/ ``OUT/st.txt`` (``id<TAB>text``, input order).  ``DATA`` + ``config.yaml`` supply what a trained model needs from its data
+directory: the source CMVN statistics, the target statistics for de-normalisation, the vocoder section, the dictionaries,
+the speakers.  Utterances are ordered and batched as the dataset does it (longest first, ties in input order, the native
+``batch_by_size`` over frame counts), so the outputs are those of stage 3 + ``generate_waveform`` on the same audio, bit for
+bit (tests/test_translate.py).  ``--manifest``: a TSV with the columns ``id``, ``audio`` and optionally ``speaker``.
+
+Refused, each with a message: a model without the requested text head, ``--use-hubert`` models (they take raw audio; the
+recipes infer with ``--use-hubert False``), text-input models, and a config whose source transforms for inference
+(``src_transforms``: ``_eval``, else ``*``) are anything but nothing, ``global_cmvn`` or ``src_global_cmvn``.  An utterance
+too short for one frame, or longer than the model's ``max_source_positions``, is skipped with a warning and listed in the
+summary.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import os
+import sys
+import time
+import wave
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .data import audio_utils
+from .data.feature_extraction import DeviceFeatureExtractor
+from .data.synthetic import batch_by_size
+from .generate_waveform import dump_result, load_task_model
+from .runtime import binding as bd
+from .runtime import streams as _streams
+from .tasks.s2s_translation import _flag_is_true
+
+SRC_CMVN = ("global_cmvn", "src_global_cmvn")
+N_BINS = 80  # the filter bank stage 3 extracts (get_feature_manifest.py: extract_fbank_features' default)
+
+
+def make_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="s2st_amd.translate", allow_abbrev=False)
+    a = p.add_argument
+    a("data", help="the data directory the model was trained on (config.yaml, dictionaries, CMVN statistics, speakers)")
+    a("--config-yaml", default="config.yaml")
+    a("--task", default="s2s_translation")
+    a("--path", required=True, help="checkpoint (reference .pt layout)")
+    a("--results-path", required=True)
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument("--inputs", nargs="+", default=None, help="audio files; ids are the file stems")
+    g.add_argument("--manifest", default=None, help="TSV with the columns id, audio and optionally speaker")
+    a("--src-sample-rate", type=int, default=None,
+      help="the rate the model's source features were extracted at; inputs at other rates are resampled on the device "
+           "(default: all inputs must share one rate and are taken at it)")
+    a("--output-sample-rate", type=int, default=None, help="resample the generated audio (default: the feature rate)")
+    a("--speaker", default=None, help="speaker name for inputs without one (speaker-conditioned models)")
+    a("--text", default="none", choices=["none", "asr", "st", "both"], help="also decode the aux ASR and / or ST head")
+    a("--beam", type=int, default=5)
+    a("--max-len-b", type=int, default=200, help="text heads: tokens at most (generate_text's flag)")
+    a("--max-tokens", type=int, default=None)
+    a("--batch-size", "--max-sentences", type=int, default=None, dest="batch_size")
+    a("--vocoder", default="griffin_lim", choices=["griffin_lim", "hifigan"])
+    a("--spec-bwd-max-iter", type=int, default=8)
+    a("--eos-prob-threshold", type=float, default=0.5)
+    a("--max-target-positions", type=int, default=None, help="AR steps at most (default: the checkpoint's value)")
+    a("--seed", type=int, default=None, help="seed numpy's generator (Griffin-Lim's initial phases) before translating")
+    a("--dump-features", action="store_true")
+    a("--dump-attentions", action="store_true")
+    a("--dump-eos-probs", action="store_true")
+    a("--precise-gemm", action="store_true", help="bf16x3 GEMMs (fp32-accurate; parity runs)")
+    return p
+
+
+def write_pcm16(path: str, pcm: np.ndarray, sample_rate: int) -> None:
+    """16-bit PCM mono, the container ``generate_waveform.write_wav`` writes."""
+    with wave.open(path, "wb") as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
+
+
+def read_audio(path: str) -> Tuple[np.ndarray, int]:
+    """``audio_utils.read_waveform`` + the mono mix-down of ``get_waveform``: float32 in [-1, 1) and the file's rate."""
+    wav, sr = audio_utils.get_waveform(path, normalization=True, mono=True, always_2d=False)
+    return np.ascontiguousarray(wav, dtype=np.float32), int(sr)
+
+
+def to_16bit_range(w: np.ndarray) -> np.ndarray:
+    """A waveform in [-1, 1) in Kaldi's 16-bit range, as stage 3 scales it (``x * 2**15`` in fp32): returned as int16 where
+    that is exactly what the samples are (decoded 16-bit PCM), else as float32."""
+    if w.dtype == np.int16:
+        return w
+    f = np.asarray(w, dtype=np.float32) * np.float32(2 ** 15)
+    if f.size and (np.abs(f).max() > 32768 or np.signbit(f[f == 0]).any()):
+        return f
+    i = np.clip(f, -32768, 32767).astype(np.int16)
+    return i if np.array_equal(i.astype(np.float32), f) else f
+
+
+def pcm16(waves: Sequence[torch.Tensor], device) -> List[np.ndarray]:
+    """``s2st_wave_to_pcm16`` over a ragged batch of device waveforms and ONE int16 copy to the host."""
+    lens = [int(w.numel()) for w in waves]
+    B, N = len(waves), max(lens, default=0)
+    if B == 0 or N == 0:
+        return [np.zeros(0, np.int16) for _ in waves]
+    x = torch.zeros(B, N, dtype=torch.float32, device=device)
+    for b, w in enumerate(waves):
+        x[b, :lens[b]] = w.reshape(-1)
+    ln = torch.tensor(lens, dtype=torch.int32).to(device)
+    out = torch.empty(B, N, dtype=torch.int16, device=device)
+    bd.call("s2st_wave_to_pcm16", x, ln, out, B, N)
+    host = out.cpu().numpy()
+    return [host[b, :lens[b]] for b in range(B)]
+
+
+class SpeechTranslator:
+    """The translator behind the CLI.  ``from_checkpoint`` builds it; ``translate`` takes waveforms and returns, per input,
+    the generator's hypothesis dict (``feature``, ``attn``, ``eos_prob``, ``alignment``, ``waveform``: device tensors at the
+    feature rate) with ``id``, ``src_feature`` (the encoder's input rows), ``pcm`` (int16 numpy at ``sample_rate``),
+    ``sample_rate`` and the ``asr`` / ``st`` strings of the requested text heads -- or ``None`` for a skipped input (``skipped``: [(id, reason)] of the last call)."""
+
+    def __init__(self, task, model, margs, device, src_sample_rate: Optional[int] = None,
+                 output_sample_rate: Optional[int] = None, text: str = "none", beam: int = 5,
+                 max_tokens: Optional[int] = None, batch_size: Optional[int] = None,
+                 max_len_b: int = 200, text_max_positions: Optional[int] = None, cmvn=None):
+        """``cmvn``: (mean, std) fp32 [80] instead of the data config's source statistics (a model built without a data
+        directory: tools/translate_rate.py)."""
+        eng = model.engine
+        if getattr(model, "hubert", None) is not None:
+            raise SystemExit("translate: a --use-hubert model takes raw audio, not filter-bank features; the recipes infer "
+                             "with --use-hubert False")
+        if eng.cfg.text_input or _flag_is_true(getattr(margs, "input_text", "false")):
+            raise SystemExit("translate: the checkpoint is a text-input model (--input-text true): it has no speech to translate")
+        self.task, self.model, self.margs, self.device = task, model, margs, torch.device(device)
+        self.src_sample_rate, self.output_sample_rate = src_sample_rate, output_sample_rate
+        self.heads = {"none": (), "asr": ("asr",), "st": ("st",), "both": ("asr", "st")}[text]
+        for which in self.heads:
+            if not (eng.cfg.has_asr if which == "asr" else eng.cfg.has_st):
+                raise SystemExit(f"translate: --text {text} needs the aux {which.upper()} decoder, which this model does not have")
+        if max_tokens is None and batch_size is None:
+            max_tokens = 8000  # generate_waveform's default
+        self.max_tokens, self.batch_size = max_tokens, batch_size
+        self.max_source_positions = int(getattr(margs, "max_source_positions", 3000))
+        self.extractor = DeviceFeatureExtractor(self.device)
+        self.mean, self.std = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
+                               for x in (cmvn if cmvn is not None else self._source_cmvn(task.data_cfg)))
+        self.generator = task.build_generator_tts([model], margs)
+        self.sample_rate = int(task.sr)
+        self.vocoder_name = getattr(margs, "vocoder", None) or "griffin_lim"
+        self.text_generators = {}
+        for which in self.heads:
+            # (the text decoders' position limit is the checkpoint's max_target_positions, as in generate_text: the
+            # generation-time --max-target-positions bounds the AR mel steps only)
+            ga = argparse.Namespace(aux_decoder=which, beam=beam, search="device", max_len_b=max_len_b)
+            self.text_generators[which] = task.build_generator(
+                [model], ga, extra_gen_cls_kwargs={"max_len": int(text_max_positions or 0)})
+        self.skipped: List[Tuple[str, str]] = []
+        self.seconds = {"front_end": 0.0, "generate": 0.0}
+
+    # ---- construction ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _source_cmvn(data_cfg) -> Tuple[np.ndarray, np.ndarray]:
+        """(mean, std) fp32 [80] of the config's source transform at inference; no transform: (0, 1), which leaves the
+        filter bank's bits as they are."""
+        if data_cfg is None:
+            raise SystemExit("translate: DATA must be the model's data directory (config.yaml, dictionaries, CMVN statistics)")
+        names = data_cfg.get_feature_transforms_for_src("", False).get("src_transforms") or []
+        if len(names) == 0:
+            return np.zeros(N_BINS, np.float32), np.ones(N_BINS, np.float32)
+        if len(names) != 1 or names[0] not in SRC_CMVN:
+            raise SystemExit(f"translate: the config's source transforms at inference are {list(names)}; only none, "
+                             f"global_cmvn or src_global_cmvn run on this path (they are fused into the feature kernel)")
+        section = data_cfg._auto_convert_to_abs_path(data_cfg.config.get(names[0]) or {})
+        path = section.get("stats_npz_path")
+        if path is None or not os.path.isfile(path):
+            raise SystemExit(f"translate: {names[0]}: stats_npz_path {path!r} not found")
+        stats = np.load(path)
+        out = []
+        for k in ("mean", "std"):
+            v = np.asarray(stats[k]).reshape(-1)
+            v32 = v.astype(np.float32)
+            if v.shape[0] != N_BINS or not np.array_equal(v32.astype(v.dtype), v):
+                # (float64 statistics would make the host transform a float64 operation: not what the kernel computes)
+                raise SystemExit(f"translate: {path}: '{k}' must hold {N_BINS} float32 values")
+            out.append(np.ascontiguousarray(v32))
+        return out[0], out[1]
+
+    @classmethod
+    def from_checkpoint(cls, data: str, path: str, config_yaml: str = "config.yaml", device=None, task: str = "s2s_translation",
+                        precise_gemm: bool = False, vocoder: str = "griffin_lim", spec_bwd_max_iter: int = 8,
+                        eos_prob_threshold: float = 0.5,
+                        max_target_positions: Optional[int] = None, on_model_built=None, **options) -> "SpeechTranslator":
+        """The checkpoint's model on ``device`` with the generation-time flags of ``generate_waveform``; ``options``: the
+        constructor's (src_sample_rate, output_sample_rate, text, beam, max_len_b, max_tokens, batch_size)."""
+        if device is None:
+            if not torch.cuda.is_available():
+                raise SystemExit("s2st_amd.translate needs a HIP device (the product path has no CPU fallback)")
+            device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+        largs = argparse.Namespace(data=data, config_yaml=config_yaml, path=path, task=task, precise_gemm=precise_gemm)
+        trained = {}
+
+        def configure(margs):
+            # (refused before the model is built: a HuBERT front end would want its own weights)
+            if _flag_is_true(getattr(margs, "use_hubert", "false")):
+                raise SystemExit("translate: a --use-hubert model takes raw audio, not filter-bank features; the recipes "
+                                 "infer with --use-hubert False")
+            if _flag_is_true(getattr(margs, "input_text", "false")):
+                raise SystemExit("translate: the checkpoint is a text-input model (--input-text true): it has no speech to "
+                                 "translate")
+            trained["text_max_positions"] = getattr(margs, "max_target_positions", None)
+            margs.eos_prob_threshold = eos_prob_threshold
+            margs.spec_bwd_max_iter = spec_bwd_max_iter
+            margs.gl_phase_rng = "numpy"  # (the reference's draws, as generate_waveform's default)
+            margs.vocoder = vocoder
+            if max_target_positions is not None:
+                margs.max_target_positions = max_target_positions
+
+        tk, model, margs = load_task_model(largs, device, configure, on_model_built)
+        return cls(tk, model, margs, device, **dict(trained, **options))
+
+    # ---- the pipeline ---------------------------------------------------------------------------------------------------
+    def _frames(self, n: int, rate: int) -> int:
+        shift, size = self.extractor._fbank_tables(rate, N_BINS)[:2]
+        return 0 if n < size else 1 + (n - size) // shift
+
+    def _source_rate(self, rates: Sequence[int]) -> int:
+        if self.src_sample_rate is not None:
+            return int(self.src_sample_rate)
+        if len(set(rates)) > 1:
+            raise SystemExit(f"translate: the inputs come at several sample rates {sorted(set(rates))}: pass --src-sample-rate "
+                             f"(the rate the model's features were extracted at) to have them resampled")
+        return int(rates[0])
+
+    def _front_end(self, waves, rates, rate: int):
+        """One batch: (resample ->) 2**15 scale -> fbank_batch, in the stage's order.  Returns (src, frames) on the device."""
+        from .models.wav2vec2_ctc import resample
+        scaled = [None] * len(waves)
+        for r in sorted({r for r in rates if r != rate}):
+            idx = [i for i, x in enumerate(rates) if x == r]
+            for i, y in zip(idx, resample([np.asarray(waves[i], dtype=np.float32) if waves[i].dtype != np.int16
+                                           else waves[i].astype(np.float32) / np.float32(32768) for i in idx], r, rate,
+                                          device=self.device)):
+                scaled[i] = y * float(2 ** 15)
+        if any(s is not None for s in scaled):
+            # (a batch with resampled members lives on the device as fp32; the others join it there)
+            for i, w in enumerate(waves):
+                if scaled[i] is None:
+                    scaled[i] = torch.from_numpy(np.asarray(to_16bit_range(w), dtype=np.float32)).to(self.device)
+        else:
+            scaled = [to_16bit_range(w) for w in waves]
+        return self.extractor.fbank_batch(scaled, rate, self.mean, self.std, N_BINS)
+
+    def _run(self, audio, ids, speakers, sink) -> None:
+        """Translate ``audio`` [(samples, rate)]; ``sink(position, hypo)`` is called once per translated input."""
+        dev = self.device
+        self.skipped = []
+        self.seconds = {"front_end": 0.0, "generate": 0.0}
+        if len(audio) == 0:
+            return
+        rates = [int(r) for _, r in audio]
+        rate = self._source_rate(rates)
+        waves = []
+        for w, _ in audio:
+            w = np.asarray(w)
+            if w.ndim != 1:
+                raise ValueError("translate takes mono waveforms (1-D arrays)")
+            waves.append(w if w.dtype == np.int16 else np.ascontiguousarray(w, dtype=np.float32))
+        lens = [int(w.shape[0]) if r == rate else -(-int(w.shape[0]) * rate // r) for w, r in zip(waves, rates)]  # resample()'s
+        n_frames = np.array([self._frames(n, rate) for n in lens], dtype=np.int64)
+        spk_ids = None
+        if speakers is not None and any(s is not None for s in speakers):
+            table = self.task.speaker_to_id
+            if table is None:  # (as the dataset: without --speaker-to-id the speaker column is not read)
+                print("translate: the model was trained without --speaker-to-id: speakers are ignored", file=sys.stderr)
+            else:
+                for s in speakers:
+                    if s not in table:
+                        raise SystemExit(f"translate: unknown speaker {s!r} (the model knows {sorted(table)})")
+                spk_ids = [int(table[s]) for s in speakers]
+        # the dataset's order and batches: longest first, ties in input order (S2STDataset.ordered_indices), size filter, the
+        # native max-tokens batcher over frame counts (S2ST_TranslationTask.get_batch_iterator)
+        order = np.lexsort([np.arange(len(waves)), -n_frames])
+        keep = []
+        for i in order:
+            if n_frames[i] == 0:
+                self.skipped.append((ids[i], "too short for one frame"))
+            elif n_frames[i] > self.max_source_positions:
+                self.skipped.append((ids[i], f"{int(n_frames[i])} frames exceed max_source_positions {self.max_source_positions}"))
+            else:
+                keep.append(int(i))
+        for i, why in self.skipped:
+            print(f"translate: skipping {i}: {why}", file=sys.stderr)
+        if not keep:
+            return
+        keep = np.asarray(keep, dtype=np.int64)
+        batches = batch_by_size(keep, n_frames[keep], self.max_tokens or 0, self.batch_size or -1, 1)
+
+        def samples():
+            for b in batches:
+                # (the collater's own sort of a batch, s2st_dataset.py:328-331: rows by descending length)
+                _, o = torch.tensor([int(n_frames[i]) for i in b], dtype=torch.long).sort(descending=True)
+                rows = [int(b[j]) for j in o.tolist()]
+                t0 = time.perf_counter()
+                src, frames = self._front_end([waves[i] for i in rows], [rates[i] for i in rows], rate)
+                self.seconds["front_end"] += time.perf_counter() - t0
+                speaker = None if spk_ids is None else torch.tensor([spk_ids[i] for i in rows], dtype=torch.long).view(-1, 1)
+                # (the lengths also as the host tensor the collater makes: the engine sizes its launches from them)
+                host_lens = torch.tensor([int(n_frames[i]) for i in rows], dtype=torch.long)
+                yield {"id": torch.tensor(rows, dtype=torch.long), "nsentences": len(rows), "speaker": speaker, "frames": frames,
+                       "net_input": {"src_speech": src, "src_speech_lens": host_lens, "speaker": speaker}}
+
+        def finish(sample, hypos):
+            if hasattr(hypos, "wait"):
+                hypos.wait()  # (the vocoder ran on the generator's second stream, beside the next batch's decoding)
+            outs = [h["waveform"] for h in hypos]
+            out_rate = self.sample_rate
+            if all(w is not None for w in outs):
+                if self.output_sample_rate not in (None, self.sample_rate):
+                    from .models.wav2vec2_ctc import resample
+                    out_rate = int(self.output_sample_rate)
+                    outs = resample(outs, self.sample_rate, out_rate, device=dev)
+                pcm = pcm16(outs, dev)
+            else:
+                pcm = [None] * len(outs)
+            for row, (i, hypo) in enumerate(zip(sample["id"].tolist(), hypos)):
+                hypo = dict(hypo, id=ids[i], pcm=pcm[row], sample_rate=out_rate,
+                            src_feature=sample["net_input"]["src_speech"][row, :int(n_frames[i])])
+                for which in self.heads:
+                    hypo[which] = sample["text"][which][row]
+                sink(i, hypo)
+
+        # driven as generate_waveform drives its generator: batch k's files are written after batch k + 1 has been enqueued
+        # (deferred vocoder), and several batches are decoded at once where the generator has that form
+        defer = dev.type == "cuda" and os.environ.get("S2ST_DEFER_VOCODER", "1") != "0"
+        chains = _streams.default_decode_chains() if (defer and hasattr(self.generator, "generate_many")) else 1
+        held, group = [], []
+
+        def flush():
+            nonlocal held, group
+            if not group:
+                return
+            t0 = time.perf_counter()
+            if len(group) >= 2:
+                hyps = list(self.generator.generate_many(self.model, group, has_targ=False, defer_vocoder=defer))
+            else:
+                hyps = [self.generator.generate(self.model, group[0], has_targ=False, defer_vocoder=defer)]
+            self.seconds["generate"] += time.perf_counter() - t0
+            for h in held:
+                finish(*h)
+            held = list(zip(group, hyps))
+            group = []
+            if not defer:
+                for h in held:
+                    finish(*h)
+                held = []
+
+        for sample in samples():
+            sample["text"] = {}
+            for which, gen in self.text_generators.items():
+                hyps = gen.generate([self.model], sample)
+                sample["text"][which] = [gen.tgt_dict.string(h[0]["tokens"].int().cpu()) for h in hyps]
+            group.append(sample)
+            if len(group) == chains:
+                flush()
+        flush()
+        for h in held:
+            finish(*h)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+
+    def translate(self, audio: Sequence[Tuple[np.ndarray, int]], ids: Optional[Sequence[str]] = None,
+                  speakers: Optional[Sequence[Optional[str]]] = None) -> List[Optional[Dict]]:
+        """``audio``: [(samples, rate)] -- mono float waveforms in [-1, 1), or int16 PCM.  Returns one entry per input, in
+        input order (``None`` for a skipped one)."""
+        ids = [str(i) for i in ids] if ids is not None else [str(i) for i in range(len(audio))]
+        if len(ids) != len(audio) or (speakers is not None and len(speakers) != len(audio)):
+            raise ValueError("translate: ids / speakers must have one entry per input")
+        if len(set(ids)) != len(ids):
+            raise SystemExit(f"translate: duplicate ids {sorted({i for i in ids if ids.count(i) > 1})}")
+        out: List[Optional[Dict]] = [None] * len(audio)
+
+        def sink(i, hypo):
+            out[i] = hypo
+
+        self._run(audio, ids, speakers, sink)
+        return out
+
+
+def read_manifest(path: str) -> Tuple[List[str], List[str], Optional[List[str]]]:
+    with open(path) as f:
+        rows = list(csv.DictReader(f, delimiter="\t", quotechar=None, doublequote=False, lineterminator="\n",
+                                   quoting=csv.QUOTE_NONE))
+    if not rows or "id" not in rows[0] or "audio" not in rows[0]:
+        raise SystemExit(f"translate: {path} must be a TSV with the columns id, audio and optionally speaker")
+    root = Path(path).parent
+    files = [r["audio"] if os.path.isabs(r["audio"]) or os.path.exists(r["audio"]) else (root / r["audio"]).as_posix()
+             for r in rows]
+    return [r["id"] for r in rows], files, ([r["speaker"] for r in rows] if "speaker" in rows[0] else None)
+
+
+def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None, on_model_built=None) -> Dict:
+    args = make_parser().parse_args(argv)
+    if args.manifest is not None:
+        ids, files, speakers = read_manifest(args.manifest)
+    else:
+        files, speakers = list(args.inputs), None
+        ids = [Path(f).stem for f in files]
+    if len(set(ids)) != len(ids):
+        raise SystemExit(f"translate: duplicate ids {sorted({i for i in ids if ids.count(i) > 1})}: two inputs would be written "
+                         f"to the same file")
+    if speakers is None and args.speaker is not None:
+        speakers = [args.speaker] * len(files)
+    elif speakers is not None:
+        speakers = [s or args.speaker for s in speakers]
+    tr = SpeechTranslator.from_checkpoint(
+        args.data, args.path, config_yaml=args.config_yaml, device=device, task=args.task, precise_gemm=args.precise_gemm,
+        vocoder=args.vocoder, spec_bwd_max_iter=args.spec_bwd_max_iter,
+        eos_prob_threshold=args.eos_prob_threshold, max_target_positions=args.max_target_positions,
+        on_model_built=on_model_built, src_sample_rate=args.src_sample_rate, output_sample_rate=args.output_sample_rate,
+        text=args.text, beam=args.beam, max_len_b=args.max_len_b, max_tokens=args.max_tokens, batch_size=args.batch_size)
+    audio = [read_audio(f) for f in files]
+    if args.seed is not None:
+        np.random.seed(args.seed)
+    out_root = Path(args.results_path)
+    out_root.mkdir(exist_ok=True, parents=True)
+    out_rate = tr.sample_rate if args.output_sample_rate is None else int(args.output_sample_rate)
+    wav_dir = out_root / f"wav_{out_rate}hz_{args.vocoder}"
+    wav_dir.mkdir(exist_ok=True, parents=True)
+    dargs = argparse.Namespace(results_path=args.results_path, dump_features=args.dump_features, dump_target=False,
+                               dump_attentions=args.dump_attentions, dump_eos_probs=args.dump_eos_probs, dump_plots=False,
+                               dump_waveforms=False, audio_format="wav")
+    written: List[str] = []
+    texts: Dict[str, Dict[int, str]] = {which: {} for which in tr.heads}
+    n_utt = n_frames = 0
+
+    def sink(i, hypo):
+        nonlocal n_utt, n_frames
+        dump_result(dargs, args.vocoder, out_rate, ids[i], hypo, written)
+        if hypo["pcm"] is not None:
+            path = str(wav_dir / f"{ids[i]}.wav")
+            write_pcm16(path, hypo["pcm"], out_rate)
+            written.append(path)
+        for which in tr.heads:
+            texts[which][i] = hypo[which]
+        n_utt += 1
+        n_frames += int(hypo["feature"].shape[0])
+
+    t0 = time.perf_counter()
+    tr._run(audio, ids, speakers, sink)
+    seconds = time.perf_counter() - t0
+    for which in tr.heads:
+        path = str(out_root / f"{which}.txt")
+        with open(path, "w", encoding="utf-8") as f:
+            for i in sorted(texts[which]):
+                f.write(f"{ids[i]}\t{texts[which][i]}\n")
+        written.append(path)
+    return {"utterances": n_utt, "mel_frames": n_frames, "seconds": seconds, "front_end_seconds": tr.seconds["front_end"],
+            "files": written, "sample_rate": out_rate, "skipped": [i for i, _ in tr.skipped],
+            "skipped_reasons": dict(tr.skipped)}
+
+
+def cli_main():
+    r = main(sys.argv[1:])
+    print(f"translated {r['utterances']} utterances ({r['mel_frames']} mel frames) in {r['seconds']:.2f} s; "
+          f"{len(r['files'])} files under the results path; skipped: {r['skipped'] or 'none'}")
+
+
+if __name__ == "__main__":
+    cli_main()
