@@ -866,6 +866,32 @@ int s2st_w2v_ctc_greedy_i32(const float* logits, const int32_t* lens, int32_t* i
 int s2st_resample_sinc_f32(const float* x, const int32_t* n_in, const float* table, float* y, int32_t B, int32_t N_in, int32_t N_out, int32_t L, int32_t M, int32_t KL, int32_t KW, void* stream);
 
 /* ======================================================================================
+ * CTC forced alignment (csrc/ctc_align.hip): the Viterbi path of a given transcript through a CTC head's log-probabilities.
+ * The reference has NO counterpart -- it never materialises an alignment; SURVEY.md section 0 item 2 leaves the definition
+ * to the build ("greedy arg-max path of lprobs and the Viterbi forced alignment; both integer").  This is the definition:
+ *   ext = blank, y0, blank, y1, .., blank (S = 2 L + 1 states, L = tgt_lens[b] clamped to [0, Lmax]);  lp[t][v] =
+ *   lprobs[b ld_b + t ld_t + v] (so [B][E][V] and [E][B][V] are both served), a NaN counts as -inf, -inf is IEEE -inf;
+ *   d[0][0] = lp[0][blank], d[0][1] = lp[0][y0], every other d[0][s] = -inf;  for t >= 1
+ *   d[t][s] = max(d[t-1][s], d[t-1][s-1], d[t-1][s-2] if ext[s] != blank and ext[s] != ext[s-2]) + lp[t][ext[s]] (one
+ *   fp32 add); a larger jump replaces a smaller one only when strictly greater (stay wins over +1, +1 over +2); with
+ *   T = in_lens[b] clamped to [0, E] the path ends in state S - 1 only if d[T-1][S-1] > d[T-1][S-2], else in S - 2 (L = 0:
+ *   state 0).  score[b] = that final d, -inf when no path exists (T < L + repeats, T = 0, or every path crosses a -inf).
+ *   frame_tok[b][t] = index 0 .. L-1 of the target token frame t emits, -1 on a blank frame, -2 for t >= T and for the
+ *   whole row of an infeasible utterance;  tok_start / tok_end[b][i] = the frames [start, end) of target token i, -1
+ *   behind tgt_lens[b] and for an infeasible utterance;  tok_score[b][i] = (fp32 sum in frame order of lp[t][y_i] over
+ *   those frames) / count, one IEEE division, 0 where the spans are -1.  Every element of every output is written.
+ * targets [B][Lmax] (an id outside [0, V) is read as the nearest valid column), S <= 2049 (S2ST_ERR_SHAPE beyond), V is
+ * unbounded (only the S columns of a frame are gathered).  route: 0 = pick, 1 = back-pointers (2 bits per frame and state)
+ * in LDS -- S2ST_ERR_SHAPE when E and Lmax do not fit 160 KiB -- 2 = in `workspace` (s2st_ctc_align_workspace BYTES;
+ * S2ST_ERR_ARG when short).  No atomics, nothing read back to the host, stream-ordered; results repeat bit for bit.
+ * ====================================================================================== */
+int64_t s2st_ctc_align_workspace(int32_t B, int32_t E, int32_t Lmax);
+int s2st_ctc_align_f32(const float* lprobs, int64_t ld_b, int64_t ld_t, const int64_t* targets, int32_t Lmax,
+                       const int32_t* in_lens, const int32_t* tgt_lens, int32_t B, int32_t E, int32_t V, int32_t blank,
+                       int32_t route, int32_t* frame_tok, int32_t* tok_start, int32_t* tok_end, float* tok_score, float* score,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ======================================================================================
  * Gradient exchange: SUM all-reduce over an RCCL communicator, one process per GPU.  Replaces the bucketed NCCL
  * all-reduce torch DDP runs for the reference (fairseq/models/distributed_fairseq_model.py:58-67); the trainer hands
  * over contiguous ranges of the flat gradient arena as the backward finishes them (s2st_engine_segment_range) and

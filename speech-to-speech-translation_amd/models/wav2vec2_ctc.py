@@ -299,3 +299,43 @@ class Wav2Vec2CTC(SpeechEncoder):
         for b, i in enumerate(keep):
             out[i] = self.decode(ids[b, :counts[b]])
         return out
+
+    FRAME_SECONDS = 0.02  # one frame per 320 samples at 16 kHz
+
+    def encode_text(self, text: str) -> List[int]:
+        """The recogniser's spelling of a text: upper case, every space a word delimiter (``decode`` strips the delimiters
+        at a transcript's ends; a text that keeps them as spaces aligns them too).  A character the vocabulary does not
+        hold is refused by name."""
+        token_to_id = {t: i for i, t in self.id_to_token.items()}
+        ids = []
+        for ch in text.upper().replace(" ", self.word_delimiter):
+            if ch not in token_to_id:
+                raise ValueError(f"align: the character {ch!r} of {text!r} is not in the recogniser's vocabulary")
+            ids.append(token_to_id[ch])
+        return ids
+
+    def align(self, waves: Sequence[torch.Tensor], texts: Sequence[str], aligner: str = "device"):
+        """Word timings of known texts in 16 kHz waveforms: per utterance a list of ``ctc_align.Segment(text, start, end,
+        score)`` with start / end in seconds (frame x 0.02) and the frame-weighted mean log-probability of the word's
+        characters; the empty list when the text has no path through the utterance's frames.  CTC forced alignment
+        (ctc_align.py: ties to the smaller jump; parity unpinned) of the characters against log-softmax of the valid
+        frames' logits.  No reference counterpart: evalute_s2s_bleu.py only transcribes."""
+        from .. import ctc_align
+        if not self.id_to_token:
+            raise ValueError("no vocabulary: build the recogniser with vocab_map (vocab.json)")
+        if len(waves) != len(texts):
+            raise ValueError(f"{len(waves)} waveforms, {len(texts)} texts")
+        targets = [self.encode_text(t) for t in texts]
+        logits, frame_lens, _, _ = self.forward(waves)
+        B, T, V = logits.shape
+        lprobs = torch.empty_like(logits)  # (rows behind an utterance's frames stay unwritten: the aligner never reads them)
+        for b in range(B):
+            bd.call("s2st_log_softmax_rows_f32", logits[b], V, lprobs[b], V, frame_lens[b], V, 1)
+        als = ctc_align.forced_align(lprobs, targets, frame_lens, blank=self.pad_token_id, layout="BTV", aligner=aligner)
+        out = []
+        for al, ids in zip(als, targets):
+            words = ctc_align.segments(al, [self.id_to_token[i] for i in ids], sep=self.word_delimiter)
+            out.append([ctc_align.Segment(w.text, w.start * self.FRAME_SECONDS, w.end * self.FRAME_SECONDS, w.score)
+                        for w in words])
+        self.last_alignments = als
+        return out
