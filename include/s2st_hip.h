@@ -892,6 +892,40 @@ int s2st_ctc_align_f32(const float* lprobs, int64_t ld_b, int64_t ld_t, const in
                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ======================================================================================
+ * Pause-seeking segmentation of long recordings (csrc/segment.hip): where to cut a recording that is longer than the model
+ * takes, so that the cuts fall into pauses.  The reference has NO counterpart (it only ever sees utterances), so the
+ * definition is this library's own; segmentation.host_segment restates it in numpy / Python ints and the two agree bit for bit.
+ * Everything is int64 and exact:
+ *   x = recording b's 16-bit PCM, pcm[soff[b] .. soff[b + 1]), n samples; frames as the Kaldi filter bank counts them:
+ *   T = 0 if n < win, else 1 + (n - win) / hop (clamped to Tmax);
+ *   E[t] = sum_{i < win} x[t hop + i]^2;   S[t] = sum_{u = max(0, t - w)}^{min(T - 1, t + w)} E[u];
+ *   lambda = floor((double)max_t S[t] * penalty_factor),  thr = floor((double)max_t E[t] * silence_factor): one IEEE double
+ *   multiply and a floor each (2^62 where the product reaches 2^62; both maxima are 0 for T = 0);
+ *   cut frames 0 = b_0 < b_1 < .. < b_K = T with min_len <= b_{k+1} - b_k <= max_len minimise sum over the interior cuts of
+ *   (S[b_k] + lambda):  D[0] = 0,  D[t] = S[t] + lambda + min_{max(0, t - max_len) <= s <= t - min_len} D[s] (0 < t < T),
+ *   D[T] = that minimum alone; a t without a reachable s is unreachable and enters no sum.  TIES GO TO THE SMALLEST s at
+ *   every step (the fewest, latest cuts).  T < min_len: one segment [0, T) without a search.  cost[b] = D[T] (0 then).
+ *   A frame is speech if E[t] > thr; segment k is narrowed to trim_start = max(b_k, first - pad), trim_end = min(b_{k+1},
+ *   last + 1 + pad) around its first / last speech frame; without one it is dropped (dropped = 1, trim_start = trim_end = b_k).
+ * Needs 1 <= min_len, 2 min_len <= max_len (then every T >= min_len is feasible), 0 <= w <= 64, pad >= 0, 1 <= hop, 1 <= win,
+ * finite factors >= 0, B <= 65535, Kcap >= max(1, Tmax / min_len): S2ST_ERR_ARG otherwise.  max_len + min_len <= 7168
+ * (the search keeps that many D in LDS, under 64 KiB): S2ST_ERR_SHAPE beyond.  The sums stay below 2^63 while (T / min_len) (1 +
+ * penalty_factor) (2 w + 1) win < 2^33.
+ * Outputs: nseg [B]; seg_start / seg_end / trim_start / trim_end [B][Kcap] int32 in frames (-1 behind nseg[b]), dropped
+ * [B][Kcap] int32 (0 behind); cost [B] int64.  Every element of every output is written.  Segment k covers the samples
+ * [b_k hop, b_{k+1} hop), the last one to n.
+ * workspace: s2st_segment_workspace BYTES, 8-byte aligned; after the call it holds E [B][Tmax] and S [B][Tmax] int64 at its
+ * start (rows beyond T are not written).  Two launches (energy: parallel over frames; search: one workgroup per recording,
+ * min_len frames per barrier), no atomics, nothing read back to the host, stream-ordered; results repeat bit for bit.
+ * ====================================================================================== */
+int64_t s2st_segment_workspace(int32_t B, int32_t Tmax, int32_t min_len);
+int s2st_segment_pcm16(const int16_t* pcm, const int64_t* soff, int32_t B, int32_t Tmax, int32_t win, int32_t hop, int32_t w,
+                       int32_t min_len, int32_t max_len, int32_t pad, double penalty_factor, double silence_factor,
+                       int32_t Kcap, int32_t* nseg, int32_t* seg_start, int32_t* seg_end, int32_t* trim_start,
+                       int32_t* trim_end, int32_t* dropped, int64_t* cost, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+/* ======================================================================================
  * Gradient exchange: SUM all-reduce over an RCCL communicator, one process per GPU.  Replaces the bucketed NCCL
  * all-reduce torch DDP runs for the reference (fairseq/models/distributed_fairseq_model.py:58-67); the trainer hands
  * over contiguous ranges of the flat gradient arena as the backward finishes them (s2st_engine_segment_range) and

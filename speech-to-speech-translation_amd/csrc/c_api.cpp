@@ -404,6 +404,10 @@ int s2st_feature_moments_f32(const float* feats, const int32_t* offsets, float* 
 int s2st_wave_to_pcm16(const float* wave, const int32_t* len, int16_t* pcm, int32_t B, int32_t N, void* stream) {
   return s2st_wave_pcm16(wave, len, pcm, B, N, (hipStream_t)stream);
 }
+int64_t s2st_segment_workspace(int32_t B, int32_t Tmax, int32_t min_len) { return s2st_segment_ws_bytes(B, Tmax, min_len); }
+int s2st_segment_pcm16(const int16_t* pcm, const int64_t* soff, int32_t B, int32_t Tmax, int32_t win, int32_t hop, int32_t w, int32_t min_len, int32_t max_len, int32_t pad, double penalty_factor, double silence_factor, int32_t Kcap, int32_t* nseg, int32_t* seg_start, int32_t* seg_end, int32_t* trim_start, int32_t* trim_end, int32_t* dropped, int64_t* cost, void* workspace, int64_t workspace_bytes, void* stream) {
+  return s2st_segment_speech(pcm, soff, B, Tmax, win, hop, w, min_len, max_len, pad, penalty_factor, silence_factor, Kcap, nseg, seg_start, seg_end, trim_start, trim_end, dropped, cost, workspace, workspace_bytes, (hipStream_t)stream);
+}
 #ifndef S2ST_SOURCE_HASH
 #define S2ST_SOURCE_HASH "unknown"  // (__graft_entry__.build passes the hash of the sources; the test emulator build does not)
 #endif

@@ -356,6 +356,16 @@ int s2st_feature_moments(const float* feats, const int* offs, float* mom, int U,
 int s2st_wave_pcm16(const float* wave, const int* len, int16_t* pcm, int B, int N, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// Pause-seeking segmentation of long recordings (segment.hip; the definition is in include/s2st_hip.h): frame energies and
+// their maxima over a ragged batch of 16-bit PCM, then the exact search for the cheapest cuts, one workgroup per recording
+// ---------------------------------------------------------------------------------------
+int64_t s2st_segment_ws_bytes(int B, int Tmax, int min_len);
+int s2st_segment_speech(const int16_t* pcm, const int64_t* soff, int B, int Tmax, int win, int hop, int w, int min_len,
+                        int max_len, int pad, double penalty_factor, double silence_factor, int Kcap, int* nseg, int* seg_start,
+                        int* seg_end, int* trim_start, int* trim_end, int* dropped, int64_t* cost, void* workspace,
+                        int64_t workspace_bytes, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh
 // ---------------------------------------------------------------------------------------
 // y[b][q up + r][o] = epilogue(bias[o] + sum_{c, j} in[b][q + off[r] + j dil][c] * w[r][o][j][c]) for q < nq; input rows

@@ -368,7 +368,7 @@ def flash_attention(q, k, v, H, *, klen=None, causal=False, scale=None, drop_p=0
 import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "s2st_hip.h")
-_CT = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
+_CT = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double,
        "int": C.c_int, "s2st_split": Split}
 _protos = None
 

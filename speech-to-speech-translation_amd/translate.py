@@ -23,6 +23,17 @@ recipes infer with ``--use-hubert False``), text-input models, and a config whos
 (``src_transforms``: ``_eval``, else ``*``) are anything but nothing, ``global_cmvn`` or ``src_global_cmvn``.  An utterance
 too short for one frame, or longer than the model's ``max_source_positions``, is skipped with a warning and listed in the
 summary.
+
+``--segment long`` (default ``off``: the above) translates the long ones too: an input of more frames than
+``min(max_source_positions, --max-segment-s)`` is cut at its pauses (segmentation.py: an exact integer optimisation over the
+filter bank's frames, on the device or with ``--segmenter host`` in numpy, bit-equal; at the source rate, after any
+resampling), and its trimmed segments that hold speech enter the ordering and batching above as inputs ``id#k`` among the
+others.  ``OUT/wav_.../<id>.wav`` then holds the segments' PCM in order -- in front of each from the second on a pause of zeros,
+``min(gap_src_samples * out_rate // src_rate, --max-pause-ms)`` long, the gap being the source distance between the neighbours'
+trimmed spans -- ``asr.txt`` / ``st.txt`` one line per recording (the segments' strings joined by a space), and
+``OUT/segments.tsv`` one row per segment: ``id, k, src_start_s, src_end_s, trim_start_s, trim_end_s, dropped, out_start_s,
+out_end_s`` and the text columns.  The dumps are per segment (``id#k``).  A recording without any speech is skipped and listed.
+**Parity unpinned: the reference has no segmentation.**
 """
 from __future__ import annotations
 
@@ -38,6 +49,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import segmentation as sgm
 from .data import audio_utils
 from .data.feature_extraction import DeviceFeatureExtractor
 from .data.synthetic import batch_by_size
@@ -80,7 +92,46 @@ def make_parser() -> argparse.ArgumentParser:
     a("--dump-attentions", action="store_true")
     a("--dump-eos-probs", action="store_true")
     a("--precise-gemm", action="store_true", help="bf16x3 GEMMs (fp32-accurate; parity runs)")
+    add_segment_flags(p)
+    a("--segment", default="off", choices=["off", "long"],
+      help="long: an input longer than the model takes is cut at its pauses (segmentation.py) and translated segment by "
+           "segment; off: it is skipped")
+    a("--max-pause-ms", type=float, default=sgm.MAX_PAUSE_MS,
+      help="--segment long: the silence written between two segments' translations is the source pause, this long at most")
     return p
+
+
+def add_segment_flags(p: argparse.ArgumentParser) -> None:
+    """The segmentation's own flags (shared with ``python -m s2st_amd.segment``)."""
+    a = p.add_argument
+    a("--max-segment-s", type=float, default=None, help="segments last this long at most (default: what the model takes)")
+    a("--min-segment-s", type=float, default=sgm.MIN_SEGMENT_S, help="... and this long at least")
+    a("--silence-db", type=float, default=sgm.SILENCE_DB,
+      help="a frame this far below the loudest frame's energy is silence (segments are trimmed to their speech)")
+    a("--cut-penalty-db", type=float, default=sgm.CUT_PENALTY_DB,
+      help="what one cut costs besides the energy it cuts through: the largest smoothed energy lowered by this")
+    a("--segment-pad-ms", type=float, default=sgm.PAD_MS, help="kept around a segment's first and last speech frame")
+    a("--segmenter", default="device", choices=["device", "host"],
+      help="s2st_segment_pcm16 on the device, or the same rules in numpy on the host (same files)")
+
+
+def segment_frames(args_or_opts, limit: Optional[int]) -> Dict:
+    """The flags in frames of 10 ms: {min_len, max_len, pad, silence_db, cut_penalty_db, segmenter}.  ``limit``: the
+    model's ``max_source_positions`` (None: no model)."""
+    g = (lambda k, d: args_or_opts.get(k, d)) if isinstance(args_or_opts, dict) else (lambda k, d: getattr(args_or_opts, k, d))
+    max_s = g("max_segment_s", None)
+    max_len = limit if max_s is None else int(round(float(max_s) * 100))
+    if max_len is None:
+        raise SystemExit("segment: --max-segment-s is needed without a model")
+    if limit is not None:
+        max_len = min(max_len, int(limit))
+    min_len = max(1, int(round(float(g("min_segment_s", sgm.MIN_SEGMENT_S)) * 100)))
+    if max_len < 2 * min_len:
+        raise SystemExit(f"segment: segments of at most {max_len} frames cannot all last {min_len} frames or more: "
+                         f"--max-segment-s must be at least twice --min-segment-s")
+    return {"min_len": min_len, "max_len": max_len, "pad": max(0, int(round(float(g("segment_pad_ms", sgm.PAD_MS)) / 10))),
+            "silence_db": float(g("silence_db", sgm.SILENCE_DB)), "cut_penalty_db": float(g("cut_penalty_db", sgm.CUT_PENALTY_DB)),
+            "segmenter": g("segmenter", "device")}
 
 
 def write_pcm16(path: str, pcm: np.ndarray, sample_rate: int) -> None:
@@ -135,7 +186,8 @@ class SpeechTranslator:
     def __init__(self, task, model, margs, device, src_sample_rate: Optional[int] = None,
                  output_sample_rate: Optional[int] = None, text: str = "none", beam: int = 5,
                  max_tokens: Optional[int] = None, batch_size: Optional[int] = None,
-                 max_len_b: int = 200, text_max_positions: Optional[int] = None, cmvn=None):
+                 max_len_b: int = 200, text_max_positions: Optional[int] = None, cmvn=None, segment: str = "off",
+                 max_pause_ms: float = sgm.MAX_PAUSE_MS, **segment_options):
         """``cmvn``: (mean, std) fp32 [80] instead of the data config's source statistics (a model built without a data
         directory: tools/translate_rate.py)."""
         eng = model.engine
@@ -169,6 +221,15 @@ class SpeechTranslator:
                 [model], ga, extra_gen_cls_kwargs={"max_len": int(text_max_positions or 0)})
         self.skipped: List[Tuple[str, str]] = []
         self.seconds = {"front_end": 0.0, "generate": 0.0}
+        # --segment long (segmentation.py): max_segment_s, min_segment_s, silence_db, cut_penalty_db, segment_pad_ms, segmenter
+        if segment not in ("off", "long"):
+            raise ValueError(f"segment {segment!r}: expected 'off' or 'long'")
+        unknown = set(segment_options) - {"max_segment_s", "min_segment_s", "silence_db", "cut_penalty_db", "segment_pad_ms",
+                                          "segmenter"}
+        if unknown:
+            raise TypeError(f"SpeechTranslator: unknown options {sorted(unknown)}")
+        self.segment, self.max_pause_ms, self.segment_options = segment, float(max_pause_ms), dict(segment_options)
+        self.segmentations: Dict[int, sgm.Segmentation] = {}  # of the last call: {input position: its segmentation}
 
     # ---- construction ---------------------------------------------------------------------------------------------------
     @staticmethod
@@ -263,10 +324,77 @@ class SpeechTranslator:
             scaled = [to_16bit_range(w) for w in waves]
         return self.extractor.fbank_batch(scaled, rate, self.mean, self.std, N_BINS)
 
-    def _run(self, audio, ids, speakers, sink) -> None:
+    def _segment_long(self, waves, rates, rate, n_frames, ids, speakers):
+        """--segment long: every input of more frames than a segment may have is cut at its pauses (segmentation.py, at the
+        source rate, all such inputs in one call) and replaced, in place, by its trimmed segments that hold speech, as inputs
+        ``id#k``.  Returns None when no input is that long, else the expanded (waves, rates, ids, speakers), ``origin``
+        [(input, k or None)] per expanded position and ``groups`` {input: {"seg": Segmentation, "at": {k: position}}}."""
+        opt = segment_frames(self.segment_options, self.max_source_positions)
+        long_ = [i for i in range(len(waves)) if n_frames[i] > opt["max_len"]]
+        if not long_:
+            return None
+        src = {}
+        for i in long_:
+            if rates[i] == rate:
+                src[i] = waves[i]
+            else:  # resampled once, on the device; its segments then are inputs at the source rate
+                from .models.wav2vec2_ctc import resample
+                w = waves[i].astype(np.float32) / np.float32(32768) if waves[i].dtype == np.int16 else waves[i]
+                src[i] = resample([w], rates[i], rate, device=self.device)[0].cpu().numpy()
+        shift, size = self.extractor._fbank_tables(rate, N_BINS)[:2]
+        t0 = time.perf_counter()
+        segs = sgm.segment([src[i] for i in long_], rate, opt["min_len"], opt["max_len"], sgm.SMOOTH_FRAMES, opt["silence_db"],
+                           opt["cut_penalty_db"], opt["pad"], device=self.device, segmenter=opt["segmenter"], win=size, hop=shift)
+        self.seconds["segment"] = time.perf_counter() - t0
+        xw, xr, xi, xs, origin, groups = [], [], [], [], [], {}
+        for i in range(len(waves)):
+            if i not in src:
+                xw.append(waves[i]); xr.append(rates[i]); xi.append(ids[i]); origin.append((i, None))
+                xs.append(None if speakers is None else speakers[i])
+                continue
+            seg = segs[long_.index(i)]
+            groups[i] = {"seg": seg, "at": {}}
+            self.segmentations[i] = seg
+            for k in range(len(seg)):
+                if seg.dropped[k]:
+                    continue
+                a, b = (int(v) for v in seg.trim_samples[k])
+                groups[i]["at"][k] = len(xw)
+                xw.append(src[i][a:b]); xr.append(rate); xi.append(f"{ids[i]}#{k}"); origin.append((i, k))
+                xs.append(None if speakers is None else speakers[i])
+        return xw, xr, xi, (None if speakers is None else xs), origin, groups
+
+    def _join(self, name, group, got, rate):
+        """The result of a segmented input: its segments' hypotheses in order, their PCM joined -- a pause of zeros in front
+        of each segment from the second on, as long as the source distance between the neighbours' trimmed spans (in output
+        samples), ``max_pause_ms`` at most -- and their strings joined by a space."""
+        seg, ks = group["seg"], sorted(got)
+        hyps = [got[k] for k in ks]
+        out_rate = int(hyps[0]["sample_rate"])
+        max_pause = int(self.max_pause_ms * out_rate / 1000)
+        pieces, spans, pos, prev_end = [], {}, 0, None
+        for k, h in zip(ks, hyps):
+            a, b = (int(v) for v in seg.trim_samples[k])
+            if prev_end is not None:
+                pause = min((a - prev_end) * out_rate // rate, max_pause)
+                pieces.append(np.zeros(pause, np.int16))
+                pos += pause
+            n = 0 if h["pcm"] is None else int(len(h["pcm"]))
+            pieces.append(h["pcm"])
+            spans[k] = (pos, pos + n)
+            pos, prev_end = pos + n, b
+        pcm = None if any(p is None for p in pieces) else np.concatenate(pieces)
+        out = {"id": name, "segments": hyps, "segment_ids": ks, "segmentation": seg, "pcm": pcm, "sample_rate": out_rate,
+               "src_rate": int(rate), "out_spans": spans}
+        for which in self.heads:
+            out[which] = " ".join(h[which] for h in hyps)
+        return out
+
+    def _run(self, audio, ids, speakers, sink, segment: Optional[str] = None) -> None:
         """Translate ``audio`` [(samples, rate)]; ``sink(position, hypo)`` is called once per translated input."""
         dev = self.device
         self.skipped = []
+        self.segmentations = {}
         self.seconds = {"front_end": 0.0, "generate": 0.0}
         if len(audio) == 0:
             return
@@ -280,6 +408,25 @@ class SpeechTranslator:
             waves.append(w if w.dtype == np.int16 else np.ascontiguousarray(w, dtype=np.float32))
         lens = [int(w.shape[0]) if r == rate else -(-int(w.shape[0]) * rate // r) for w, r in zip(waves, rates)]  # resample()'s
         n_frames = np.array([self._frames(n, rate) for n in lens], dtype=np.int64)
+        mode = self.segment if segment is None else segment
+        if mode not in ("off", "long"):
+            raise ValueError(f"segment {mode!r}: expected 'off' or 'long'")
+        origin, groups, got, audio_ids = None, {}, {}, ids
+        expanded = self._segment_long(waves, rates, rate, n_frames, ids, speakers) if mode == "long" else None
+        if expanded is not None:
+            waves, rates, ids, speakers, origin, groups = expanded
+            lens = [int(w.shape[0]) for w in waves]  # (a segment is at the source rate; the others are as they were)
+            lens = [n if r == rate else -(-n * rate // r) for n, r in zip(lens, rates)]
+            n_frames = np.array([self._frames(n, rate) for n in lens], dtype=np.int64)
+            inner = sink
+
+            def sink(pos, hypo):  # a segment waits for its siblings; the input's joined result goes out with the last one
+                i, k = origin[pos]
+                if k is None:
+                    return inner(i, hypo)
+                got.setdefault(i, {})[k] = hypo
+                if len(got[i]) == groups[i]["expected"]:
+                    inner(i, self._join(audio_ids[i], groups[i], got.pop(i), rate))
         spk_ids = None
         if speakers is not None and any(s is not None for s in speakers):
             table = self.task.speaker_to_id
@@ -301,6 +448,10 @@ class SpeechTranslator:
                 self.skipped.append((ids[i], f"{int(n_frames[i])} frames exceed max_source_positions {self.max_source_positions}"))
             else:
                 keep.append(int(i))
+        for i, g in groups.items():  # a segmented input is translated if one of its segments is
+            g["expected"] = len(set(g["at"].values()) & set(keep))
+            if g["expected"] == 0:
+                self.skipped.append((audio_ids[i], "no speech found: every segment is silence or too short for one frame"))
         for i, why in self.skipped:
             print(f"translate: skipping {i}: {why}", file=sys.stderr)
         if not keep:
@@ -382,9 +533,12 @@ class SpeechTranslator:
             torch.cuda.synchronize(dev)
 
     def translate(self, audio: Sequence[Tuple[np.ndarray, int]], ids: Optional[Sequence[str]] = None,
-                  speakers: Optional[Sequence[Optional[str]]] = None) -> List[Optional[Dict]]:
+                  speakers: Optional[Sequence[Optional[str]]] = None, segment: Optional[str] = None) -> List[Optional[Dict]]:
         """``audio``: [(samples, rate)] -- mono float waveforms in [-1, 1), or int16 PCM.  Returns one entry per input, in
-        input order (``None`` for a skipped one)."""
+        input order (``None`` for a skipped one).  ``segment`` ("off" / "long"; default: the constructor's): with "long" an
+        input longer than the model takes is cut at its pauses and its entry is ``{"id", "segments": the hypotheses of its
+        segments ``id#k`` in order, "segment_ids": their k, "segmentation", "pcm": their PCM joined with the pauses between
+        them, "sample_rate", "src_rate", "out_spans": {k: (start, end) in pcm}}`` plus the joined ``asr`` / ``st`` strings."""
         ids = [str(i) for i in ids] if ids is not None else [str(i) for i in range(len(audio))]
         if len(ids) != len(audio) or (speakers is not None and len(speakers) != len(audio)):
             raise ValueError("translate: ids / speakers must have one entry per input")
@@ -395,8 +549,35 @@ class SpeechTranslator:
         def sink(i, hypo):
             out[i] = hypo
 
-        self._run(audio, ids, speakers, sink)
+        self._run(audio, ids, speakers, sink, segment)
         return out
+
+
+SEGMENT_COLUMNS = ["id", "k", "src_start_s", "src_end_s", "trim_start_s", "trim_end_s", "dropped"]
+
+
+def segment_rows(name: str, seg, out_spans=None, out_rate: int = 0, text=None, n_text: int = 0) -> List[List[str]]:
+    """One row per segment of ``seg`` (SEGMENT_COLUMNS; times as ``%.6f`` seconds, which identify a sample at any audio
+    rate), then, with ``out_spans`` {k: (start, end)}, where its translation lies in the written wav (empty for a segment
+    that was not translated) and, with ``text`` {k: [strings]}, the text columns."""
+    rows = []
+    for k in range(len(seg)):
+        t = [f"{int(v) / seg.rate:.6f}" for v in (*seg.samples[k], *seg.trim_samples[k])]
+        row = [name, str(k)] + t + [str(int(seg.dropped[k]))]
+        if out_spans is not None:
+            row += [f"{v / out_rate:.6f}" for v in out_spans[k]] if k in out_spans else ["", ""]
+        if text is not None:
+            row += list(text.get(k, [""] * n_text))
+        rows.append(row)
+    return rows
+
+
+def write_segments_tsv(path: str, rows, out_columns: bool = False, text: Sequence[str] = ()) -> None:
+    head = SEGMENT_COLUMNS + (["out_start_s", "out_end_s"] if out_columns else []) + list(text)
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\t".join(head) + "\n")
+        for r in rows:
+            f.write("\t".join(r) + "\n")
 
 
 def read_manifest(path: str) -> Tuple[List[str], List[str], Optional[List[str]]]:
@@ -430,7 +611,12 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         vocoder=args.vocoder, spec_bwd_max_iter=args.spec_bwd_max_iter,
         eos_prob_threshold=args.eos_prob_threshold, max_target_positions=args.max_target_positions,
         on_model_built=on_model_built, src_sample_rate=args.src_sample_rate, output_sample_rate=args.output_sample_rate,
-        text=args.text, beam=args.beam, max_len_b=args.max_len_b, max_tokens=args.max_tokens, batch_size=args.batch_size)
+        text=args.text, beam=args.beam, max_len_b=args.max_len_b, max_tokens=args.max_tokens, batch_size=args.batch_size,
+        segment=args.segment, max_pause_ms=args.max_pause_ms, max_segment_s=args.max_segment_s, min_segment_s=args.min_segment_s,
+        silence_db=args.silence_db, cut_penalty_db=args.cut_penalty_db, segment_pad_ms=args.segment_pad_ms,
+        segmenter=args.segmenter)
+    if args.segment == "long":
+        segment_frames(tr.segment_options, tr.max_source_positions)  # (a contradiction among the flags is refused up front)
     audio = [read_audio(f) for f in files]
     if args.seed is not None:
         np.random.seed(args.seed)
@@ -446,9 +632,19 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     texts: Dict[str, Dict[int, str]] = {which: {} for which in tr.heads}
     n_utt = n_frames = 0
 
+    seg_rows: Dict[int, List[List[str]]] = {}
+
     def sink(i, hypo):
         nonlocal n_utt, n_frames
-        dump_result(dargs, args.vocoder, out_rate, ids[i], hypo, written)
+        if "segments" in hypo:  # --segment long: the dumps per segment (id#k), wav and text per recording
+            for k, h in zip(hypo["segment_ids"], hypo["segments"]):
+                dump_result(dargs, args.vocoder, out_rate, h["id"], h, written)
+                n_frames += int(h["feature"].shape[0])
+            text = {k: [h[which] for which in tr.heads] for k, h in zip(hypo["segment_ids"], hypo["segments"])}
+            seg_rows[i] = segment_rows(ids[i], hypo["segmentation"], hypo["out_spans"], out_rate, text, len(tr.heads))
+        else:
+            dump_result(dargs, args.vocoder, out_rate, ids[i], hypo, written)
+            n_frames += int(hypo["feature"].shape[0])
         if hypo["pcm"] is not None:
             path = str(wav_dir / f"{ids[i]}.wav")
             write_pcm16(path, hypo["pcm"], out_rate)
@@ -456,7 +652,6 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         for which in tr.heads:
             texts[which][i] = hypo[which]
         n_utt += 1
-        n_frames += int(hypo["feature"].shape[0])
 
     t0 = time.perf_counter()
     tr._run(audio, ids, speakers, sink)
@@ -466,6 +661,13 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         with open(path, "w", encoding="utf-8") as f:
             for i in sorted(texts[which]):
                 f.write(f"{ids[i]}\t{texts[which][i]}\n")
+        written.append(path)
+    if args.segment == "long":
+        for i, seg in tr.segmentations.items():  # (a recording none of whose segments was translated keeps its rows)
+            if i not in seg_rows:
+                seg_rows[i] = segment_rows(ids[i], seg, {}, out_rate, {}, len(tr.heads))
+        path = str(out_root / "segments.tsv")
+        write_segments_tsv(path, [r for i in sorted(seg_rows) for r in seg_rows[i]], out_columns=True, text=list(tr.heads))
         written.append(path)
     return {"utterances": n_utt, "mel_frames": n_frames, "seconds": seconds, "front_end_seconds": tr.seconds["front_end"],
             "files": written, "sample_rate": out_rate, "skipped": [i for i, _ in tr.skipped],
