@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import ctc_align
-from .generate_waveform import batch_iterator, load_task_model_dataset
+from .inference_common import batch_iterator, default_device, load_task_model_dataset
 
 
 def make_parser() -> argparse.ArgumentParser:
@@ -76,9 +76,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     if args.max_tokens is None and args.batch_size is None:
         args.max_tokens = 8000  # generate_waveform's default
     if device is None:
-        if not torch.cuda.is_available():
-            raise SystemExit("s2st_amd.align needs a HIP device (the product path has no CPU fallback)")
-        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+        device = default_device("align")
     task, model, margs, dataset = load_task_model_dataset(args, device, None, on_model_built)
     if not model.engine.cfg.has_ctc:
         raise SystemExit("align: the checkpoint has no CTC head (--ctc-weight 0): there is nothing to align with")

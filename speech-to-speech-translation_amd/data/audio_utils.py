@@ -219,3 +219,21 @@ def get_features_or_waveform(path: str, need_waveform: bool = False, use_sample_
         f = io.BytesIO(data)
         return get_waveform(f, always_2d=False, output_sample_rate=use_sample_rate)[0] if need_waveform else get_fbank(f)
     raise ValueError(f'Unknown file format for "{path}"')
+
+
+def read_audio(path: str) -> Tuple[np.ndarray, int]:
+    """``read_waveform`` + the mono mix-down of ``get_waveform``: float32 in [-1, 1) and the file's rate."""
+    wav, sr = get_waveform(path, normalization=True, mono=True, always_2d=False)
+    return np.ascontiguousarray(wav, dtype=np.float32), int(sr)
+
+
+def to_16bit_range(w: np.ndarray) -> np.ndarray:
+    """A waveform in [-1, 1) in Kaldi's 16-bit range, as stage 3 scales it (``x * 2**15`` in fp32): returned as int16 where
+    that is exactly what the samples are (decoded 16-bit PCM), else as float32."""
+    if w.dtype == np.int16:
+        return w
+    f = np.asarray(w, dtype=np.float32) * np.float32(2 ** 15)
+    if f.size and (np.abs(f).max() > 32768 or np.signbit(f[f == 0]).any()):
+        return f
+    i = np.clip(f, -32768, 32767).astype(np.int16)
+    return i if np.array_equal(i.astype(np.float32), f) else f

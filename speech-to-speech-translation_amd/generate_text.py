@@ -30,7 +30,7 @@ from typing import List, Optional
 
 import torch
 
-from .generate_waveform import batch_iterator, load_task_model_dataset
+from .inference_common import batch_iterator, default_device, load_task_model_dataset
 from .scoring import REFUSED_TOKENIZERS, TOKENIZERS, build_scorer
 
 # profiles/aux_decode_rate.txt: the device form is faster than the host form beyond the spread of the repeats on both heads
@@ -96,9 +96,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     if args.max_tokens is None and args.batch_size is None:
         args.max_tokens = 12000  # generate_for_s2st.py:71-72
     if device is None:
-        if not torch.cuda.is_available():
-            raise SystemExit("s2st_amd.generate_text needs a HIP device (the product path has no CPU fallback)")
-        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+        device = default_device("generate_text")
     which = args.aux_decoder or ("st" if args.scoring == "sacrebleu" else "asr")  # :107-110
 
     def configure(margs):

@@ -18,18 +18,18 @@ infer_base`` can drive it in-process.
 from __future__ import annotations
 
 import argparse
+import functools
 import os
 import sys
-import time
-import wave
 from pathlib import Path
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 
-from . import checkpoint_utils
-from .registry import TASKS
+# (load_task_model, load_task_model_dataset, batch_iterator, dump_result and write_wav live in inference_common; tests and
+# tools take them from here too)
+from .inference_common import (batch_iterator, default_device, defer_vocoder, drive, dump_result, load_task_model,  # noqa: F401
+                               load_task_model_dataset, write_wav)
 from .runtime import streams as _streams
 
 
@@ -72,110 +72,6 @@ def make_parser() -> argparse.ArgumentParser:
     return p
 
 
-def write_wav(path: str, wave_f32: np.ndarray, sample_rate: int) -> None:
-    """16-bit PCM mono (what ``soundfile.write`` makes of a float array for .wav by default)."""
-    x = np.clip(np.asarray(wave_f32, dtype=np.float64).reshape(-1), -1.0, 1.0 - 1.0 / 32768)
-    pcm = np.round(x * 32768.0).astype("<i2")
-    with wave.open(path, "wb") as f:
-        f.setnchannels(1)
-        f.setsampwidth(2)
-        f.setframerate(int(sample_rate))
-        f.writeframes(pcm.tobytes())
-
-
-def _to_np(x):
-    return None if x is None else x.detach().cpu().numpy()
-
-
-def dump_result(args, vocoder_name: str, sample_rate: int, sample_id, hypo, written: List[str]) -> None:
-    """generate_waveform.py:67-124."""
-    out_root = Path(args.results_path)
-
-    def save(sub, name, fn):
-        d = out_root / sub
-        d.mkdir(exist_ok=True, parents=True)
-        fn(str(d / name))
-        written.append(str(d / name))
-
-    if args.dump_features:
-        save("feat", f"{sample_id}.npy", lambda p: np.save(p, _to_np(hypo["feature"])))
-        if args.dump_target:
-            save("feat_tgt", f"{sample_id}.npy", lambda p: np.save(p, _to_np(hypo["targ_feature"])))
-    if args.dump_attentions:
-        save("attn", f"{sample_id}.npy", lambda p: np.save(p, _to_np(hypo["attn"])))
-    if args.dump_eos_probs:
-        save("eos", f"{sample_id}.npy", lambda p: np.save(p, _to_np(hypo["eos_prob"])))
-    if args.dump_plots:
-        import matplotlib
-        matplotlib.use("Agg")
-        import matplotlib.pyplot as plt
-        images = [_to_np(hypo["feature"]).T, _to_np(hypo["attn"])]
-        names = ["output", "alignment"]
-        if args.dump_target:
-            images, names = [_to_np(hypo["targ_feature"]).T] + images, [f"target (idx={sample_id})"] + names
-        fig, axes = plt.subplots(len(images) + 1, 1, figsize=(8, 2.2 * (len(images) + 1)))
-        for ax, im, nm in zip(axes, images, names):
-            ax.imshow(im, aspect="auto", origin="lower", interpolation="none")
-            ax.set_title(nm, fontsize=8)
-        axes[-1].plot(_to_np(hypo["eos_prob"]))
-        axes[-1].set_title("eos prob", fontsize=8)
-        fig.tight_layout()
-        save("plot", f"{sample_id}.png", lambda p: fig.savefig(p))
-        plt.close(fig)
-    if args.dump_waveforms:
-        ext = args.audio_format
-        if hypo.get("waveform") is not None:
-            save(f"{ext}_{sample_rate}hz_{vocoder_name}", f"{sample_id}.{ext}",
-                 lambda p: write_wav(p, _to_np(hypo["waveform"]), sample_rate))
-        if args.dump_target and hypo.get("targ_waveform") is not None:
-            save(f"{ext}_{sample_rate}hz_{vocoder_name}_tgt", f"{sample_id}.{ext}",
-                 lambda p: write_wav(p, _to_np(hypo["targ_waveform"]), sample_rate))
-
-
-def load_task_model(args, device, configure=None, on_model_built=None):
-    """What the generation scripts share (generate_waveform.py:134-147, fairseq_cli/generate_for_s2st.py:83-114): the
-    checkpoint in the reference's ``.pt`` layout, the task set up from the command line with the checkpoint's model flags
-    (``configure(margs)`` applies the script's own generation-time flags), the model with the checkpoint's tensors.
-    Returns (task, model, margs)."""
-    from . import criterions, models, tasks  # noqa: F401  (fill the registries)
-    state = checkpoint_utils.load_checkpoint_to_cpu(args.path)
-    margs = state["cfg"]["model"]
-    margs = argparse.Namespace(**(vars(margs) if not isinstance(margs, dict) else margs))
-    # generation-time flags override what the checkpoint carried (checkpoint_utils.load_model_ensemble_and_task +
-    # generate_waveform.py:142-144: the task is set up from the command line, n_frames_per_step from the checkpoint)
-    margs.data, margs.config_yaml = args.data, args.config_yaml
-    margs.precise_gemm = bool(args.precise_gemm)
-    margs.eval_inference = False
-    margs.train_subset = None
-    if configure is not None:
-        configure(margs)
-    for k in ("load_pretrained_encoder_from", "load_pretrained_decoder_from"):
-        setattr(margs, k, None)  # the tensors come from the checkpoint itself
-    task = TASKS[getattr(margs, "task", None) or args.task].setup_task(margs, device=device)
-    if task.data_cfg is not None:
-        margs.src_vocab_size, margs.tgt_vocab_size = len(task.source_dictionary), len(task.target_dictionary)
-    model = task.build_model(margs)
-    model.load_state_dict(state["model"], strict=True)
-    if on_model_built is not None:
-        on_model_built(model)
-    return task, model, margs
-
-
-def load_task_model_dataset(args, device, configure=None, on_model_built=None):
-    """``load_task_model`` and the split ``--gen-subset``.  Returns (task, model, margs, dataset)."""
-    task, model, margs = load_task_model(args, device, configure, on_model_built)
-    dataset = task.load_dataset(args.gen_subset)
-    return task, model, margs, dataset
-
-
-def batch_iterator(task, dataset, args):
-    """Length-ordered max-tokens batches of the split, no shuffle (generate_waveform.py:160-170)."""
-    return task.get_batch_iterator(dataset, max_tokens=args.max_tokens, max_sentences=args.batch_size,
-                                   max_positions=(sys.maxsize, sys.maxsize),
-                                   required_batch_size_multiple=args.required_batch_size_multiple, seed=args.seed,
-                                   num_shards=args.num_shards, shard_id=args.shard_id).next_epoch_itr(shuffle=False)
-
-
 def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None, on_model_built=None,
          parser: Optional[argparse.ArgumentParser] = None, mtl: bool = False) -> Dict:
     """``mtl``: the flow of generate_waveform_mtl.py (see generate_waveform_mtl.py in this package): the task's own
@@ -189,9 +85,8 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     if args.max_tokens is None and args.batch_size is None:
         args.max_tokens = 8000  # :130-131
     if device is None:
-        if not torch.cuda.is_available():
-            raise SystemExit("s2st_amd.generate_waveform needs a HIP device (the product path has no CPU fallback)")
-        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+        device = default_device("generate_waveform")
+
     def configure(margs):
         margs.eos_prob_threshold = args.eos_prob_threshold
         margs.spec_bwd_max_iter = args.spec_bwd_max_iter
@@ -218,10 +113,11 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     Path(args.results_path).mkdir(exist_ok=True, parents=True)
     ids = getattr(dataset, "ids", None)
     written: List[str] = []
-    n_utt, n_frames, t_gen, n_batches = 0, 0, 0.0, 0
+    n_utt = n_frames = n_batches = 0
+
     def finish(sample, hypos):
         """What the reference's loop does with a batch's hypotheses (generate_waveform.py:172-183 / _mtl.py:196-205)."""
-        nonlocal n_utt, n_frames
+        nonlocal n_utt, n_frames, n_batches
         if hasattr(hypos, "wait"):
             hypos.wait()  # (the vocoder ran on the generator's second stream, beside the next batch's decoding)
         if decode_src:  # :196-200
@@ -234,57 +130,18 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
                 dump_result(args, args.vocoder, sample_rate, ids[i] if ids is not None else i, hypo, written)
                 n_frames += int(hypo["feature"].shape[0])
             n_utt += 1
+        n_batches += 1
 
-    # one batch of overlap on the GPU: batch k's files are written after batch k + 1 has been enqueued, so that its
-    # Griffin-Lim iterations run beside that batch's decoding steps (S2ST_DEFER_VOCODER=0: strictly one after the other)
-    defer = device.type == "cuda" and os.environ.get("S2ST_DEFER_VOCODER", "1") != "0"
-    # ... and two batches are DECODED at once (generate_two: the second on a twin engine and a second stream) where the
-    # generator has that form: the decoding steps of one batch leave most of the chip idle (S2ST_DECODE_CHAINS=1: one by one)
+    # batch k's files are written after batch k + 1 has been enqueued, and several batches are DECODED at once where the
+    # generator has that form (S2ST_DECODE_CHAINS=1: one by one): inference_common.drive
+    defer = defer_vocoder(device)
     chains = _streams.default_decode_chains() if (defer and not mtl and hasattr(generator, "generate_many")) else 1
-
-    def groups():
-        buf, n = [], 0
-        for sample in itr:
-            if sample is None or len(sample) == 0:
-                continue
-            buf.append(sample)
-            n += 1
-            last = bool(args.max_batches and n >= args.max_batches)
-            if len(buf) == chains or last:
-                yield buf
-                buf = []
-            if last:
-                return
-        if buf:
-            yield buf
-
-    held = []
-    t_all = time.perf_counter()
-    for group in groups():
-        t0 = time.perf_counter()
-        if len(group) >= 2:
-            hyps = list(generator.generate_many(model, group, has_targ=args.dump_target, defer_vocoder=defer))
-        elif mtl:  # generate_waveform_mtl.py:195
-            hyps = [generator.generate(model, group[0], has_targ=args.dump_target and decode_mel,
-                                       decode_source_text=decode_src, decode_target_mel=decode_mel, defer_vocoder=defer)]
-        else:
-            hyps = [generator.generate(model, group[0], has_targ=args.dump_target, defer_vocoder=defer)]
-        if device.type == "cuda" and not defer:
-            torch.cuda.synchronize(device)
-        t_gen += time.perf_counter() - t0
-        for h in held:
-            finish(*h)
-        held = list(zip(group, hyps))
-        if not defer:
-            for h in held:
-                finish(*h)
-            held = []
-        n_batches += len(group)
-    for h in held:
-        finish(*h)
-    if defer:  # (generator time cannot be told from file writing when the two overlap: the loop's wall time)
-        torch.cuda.synchronize(device)
-        t_gen = time.perf_counter() - t_all
+    one = None
+    if mtl:  # generate_waveform_mtl.py:195
+        one = functools.partial(generator.generate, decode_source_text=decode_src, decode_target_mel=decode_mel)
+    t_gen = drive(generator, model, itr, finish, chains=chains, defer=defer, generate_one=one,
+                  has_targ=args.dump_target and decode_mel, max_batches=args.max_batches,
+                  sync_device=device if device.type == "cuda" else None)
     out = {"utterances": n_utt, "mel_frames": n_frames, "generate_seconds": t_gen, "batches": n_batches,
            "files": written, "sample_rate": sample_rate}
     if decode_src:  # :207-210

@@ -173,6 +173,19 @@ def conv_out_len(n: int, k: int, stride: int = 2) -> int:
     return (n + 2 * (k // 2) - k) // stride + 1
 
 
+def valid_positions(lens: torch.Tensor, T: int) -> torch.Tensor:
+    """Positions [B, T] int32 of right-padded rows of ``lens`` valid entries: PAD + 1 .. at the valid ones, PAD behind them."""
+    t = torch.arange(T).unsqueeze(0)
+    return torch.where(t < lens.unsqueeze(1), t + PAD + 1, torch.full_like(t, PAD)).to(torch.int32)
+
+
+def subsampled_lens(lens: torch.Tensor, times: int = 2) -> torch.Tensor:
+    """Encoder lengths: floor((len - 1) / 2 + 1) per stride-2 convolution (s2st_transformer.py:126-130)."""
+    for _ in range(times):
+        lens = ((lens.float() - 1) / 2 + 1).floor().long()
+    return lens
+
+
 class Engine:
     """Owns the arenas and the native engine handle."""
 
@@ -208,8 +221,7 @@ class Engine:
         if not precise:
             self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device)
             self.lib.s2st_engine_bind_bf16(h, self.params_bf16.data_ptr())
-            import os as _os
-            if _os.environ.get("S2ST_NO_WT", "0") != "1":
+            if os.environ.get("S2ST_NO_WT", "0") != "1":
                 self.params_bf16_t = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device)
                 self.lib.s2st_engine_bind_bf16_transposed(h, self.params_bf16_t.data_ptr())
         self.workspace: Optional[torch.Tensor] = None
@@ -290,14 +302,12 @@ class Engine:
         src_lens = ni["src_speech_lens"].cpu().long()
         k = self.cfg.conv_k
         E = conv_out_len(conv_out_len(S, k), k)
-        # encoder lengths: floor((len - 1) / 2 + 1) twice (s2st_transformer.py:126-130)
-        enc_lens = src_lens.clone()
+        enc_lens = subsampled_lens(src_lens)
         # CTC input lengths come from the FBANK lengths, also when the encoder ran on HuBERT frames
         # (s2st_loss.py:231-232; models/s2st_transformer.py front_end_sample keeps them)
         ctc_src = ni.get("ctc_src_speech_lens")
         ctc_lens = (ctc_src if ctc_src is not None else src_lens).cpu().long().clone()
         for _ in range(2):
-            enc_lens = ((enc_lens.float() - 1) / 2 + 1).floor().long()
             ctc_lens = (ctc_lens - k + 2 * (k // 2)) // 2 + 1  # s2st_loss.py:231-232
         if self.cfg.has_ctc and with_loss and int(ctc_lens.max()) > E:
             # what F.ctc_loss tells the reference's user in this situation (--use-hubert with --ctc-weight > 0:
@@ -309,11 +319,6 @@ class Engine:
         D = prev.shape[1]
         tgt_lens = sample["target_lengths"].cpu().long()
 
-        def speech_pos(lens, T):
-            t = torch.arange(T).unsqueeze(0)
-            valid = t < lens.unsqueeze(1)
-            return torch.where(valid, t + PAD + 1, torch.full_like(t, PAD)).to(torch.int32)
-
         def token_pos(tok):
             m = tok.ne(PAD).int()
             return ((torch.cumsum(m, dim=1) * m) + PAD).to(torch.int32)
@@ -321,9 +326,9 @@ class Engine:
         keep = {"src": src, "prev": prev}
         keep["enc_lens"] = enc_lens.to(torch.int32).to(dev)
         keep["ctc_lens"] = ctc_lens.to(torch.int32).to(dev)
-        keep["enc_pos"] = speech_pos(enc_lens, E).contiguous().to(dev)
+        keep["enc_pos"] = valid_positions(enc_lens, E).contiguous().to(dev)
         keep["tgt_lens"] = tgt_lens.to(torch.int32).to(dev)
-        keep["dec_pos"] = speech_pos(tgt_lens, D).contiguous().to(dev)
+        keep["dec_pos"] = valid_positions(tgt_lens, D).contiguous().to(dev)
         b = Batch()
         b.B, b.S, b.D, b.E = B, S, D, E
         b.src, b.prev = src.data_ptr(), prev.data_ptr()
@@ -392,10 +397,7 @@ class Engine:
         b.src_txt_ntokens = int(sample.get("src_txt_ntokens", 0))
         b.tgt_txt_ntokens = int(sample.get("tgt_txt_ntokens", 0))
         b.training, b.want_attn = int(training), int(want_attn)
-        if seed is None:
-            seed = self.step_seed
-            self.step_seed += 1
-        b.seed = seed
+        b.seed = self._next_seed(seed)
         return b, keep
 
     def _speaker_ids(self, spk, B: int) -> Optional[torch.Tensor]:
@@ -419,14 +421,12 @@ class Engine:
         tok = sample["src_text"].cpu().long().contiguous()
         B, S = tok.shape
         lens = sample["src_text_len"].cpu().long()
-        t = torch.arange(S).unsqueeze(0)
-        pos = torch.where(t < lens.unsqueeze(1), t + PAD + 1, torch.full_like(t, PAD)).to(torch.int32)
+        pos = valid_positions(lens, S)
         # (positions from the PAD mask of the tokens themselves, t2s_transformer.py:93-95: right-padded batches)
         prev = ni["prev_output_tokens"].to(dev, torch.float32).contiguous()
         D = prev.shape[1]
         tgt_lens = sample["target_lengths"].cpu().long()
-        td = torch.arange(D).unsqueeze(0)
-        dpos = torch.where(td < tgt_lens.unsqueeze(1), td + PAD + 1, torch.full_like(td, PAD)).to(torch.int32)
+        dpos = valid_positions(tgt_lens, D)
         keep = {"prev": prev, "src_txt": tok.to(dev), "src_txt_lens": lens.to(torch.int32).to(dev),
                 "enc_lens": lens.to(torch.int32).to(dev), "enc_pos": pos.contiguous().to(dev),
                 "tgt_lens": tgt_lens.to(torch.int32).to(dev), "dec_pos": dpos.contiguous().to(dev)}
@@ -451,11 +451,24 @@ class Engine:
             b.speaker = keep["speaker"].data_ptr()
         b.ntokens = int(sample["ntokens"])
         b.training, b.want_attn = int(training), int(want_attn)
+        b.seed = self._next_seed(seed)
+        return b, keep
+
+    def _next_seed(self, seed: Optional[int]) -> int:
+        """``seed``, or the engine's own next step seed."""
         if seed is None:
             seed = self.step_seed
             self.step_seed += 1
-        b.seed = seed
-        return b, keep
+        return seed
+
+    def _planned_floats(self, geo: tuple, batch: Batch) -> int:
+        """Workspace floats of a batch geometry: planned once per ``geo``, then remembered."""
+        need = self._plan.get(geo)
+        if need is None:
+            need = self._plan[geo] = int(self.lib.s2st_engine_workspace_floats(self.h, C.byref(batch)))
+        if need < 0:
+            raise bd.S2STHipError(f"workspace planning failed ({need})")
+        return need
 
     def forward(self, sample, training: bool = True, want_attn: bool = False,
                 with_loss: bool = True, seed: Optional[int] = None) -> Dict[str, torch.Tensor]:
@@ -468,20 +481,11 @@ class Engine:
         if isinstance(sample, tuple):
             b, keep = sample
             b.training, b.want_attn = int(training), int(want_attn)
-            if seed is None:
-                seed = self.step_seed
-                self.step_seed += 1
-            b.seed = seed
+            b.seed = self._next_seed(seed)
             with_loss = with_loss and bool(b.tgt)
         else:
             b, keep = self.prepare(sample, training, want_attn, with_loss, seed)
-        geo = (b.B, b.S, b.D, b.Ls, b.Lt, bool(b.tgt), b.training)
-        need = self._plan.get(geo)
-        if need is None:
-            need = int(self.lib.s2st_engine_workspace_floats(self.h, C.byref(b)))
-            self._plan[geo] = need
-        if need < 0:
-            raise bd.S2STHipError(f"workspace planning failed ({need})")
+        need = self._planned_floats((b.B, b.S, b.D, b.Ls, b.Lt, bool(b.tgt), b.training), b)
         self._grow_workspace(need, int(need * 1.05) + 4096)
         dev, c = self.device, self.cfg
         B, D, E = b.B, b.D, b.E
@@ -565,15 +569,11 @@ class Engine:
             B, S, _ = src.shape
             k = c.conv_k
             E = conv_out_len(conv_out_len(S, k), k)
-            enc_lens = src_lens.cpu().long().clone()
-            for _ in range(2):
-                enc_lens = ((enc_lens.float() - 1) / 2 + 1).floor().long()
+            enc_lens = subsampled_lens(src_lens.cpu().long())
             keep = {"src": src}
             b.src = src.data_ptr()
-        t = torch.arange(E).unsqueeze(0)
-        enc_pos = torch.where(t < enc_lens.unsqueeze(1), t + PAD + 1, torch.full_like(t, PAD)).to(torch.int32)
         keep["enc_lens"] = enc_lens.to(torch.int32).to(dev)
-        keep["enc_pos"] = enc_pos.contiguous().to(dev)
+        keep["enc_pos"] = valid_positions(enc_lens, E).contiguous().to(dev)
         b.B, b.S, b.D, b.E = B, S, 1, E
         b.enc_lens, b.enc_pos = keep["enc_lens"].data_ptr(), keep["enc_pos"].data_ptr()
         b.ctc_in_lens = keep["enc_lens"].data_ptr()
@@ -586,17 +586,7 @@ class Engine:
         elif c.n_speakers > 0 and c.text_input:
             raise ValueError("a t2s_transformer built with --speaker-to-id needs sample['speaker']")
         # workspace: the encoder forward of this geometry (planned with the full schedule: a superset)
-        geo = ("enc", B, S)
-        need = self._plan.get(geo)
-        if need is None:
-            dry = Batch()
-            for f, _ in Batch._fields_:
-                setattr(dry, f, getattr(b, f))
-            need = int(self.lib.s2st_engine_workspace_floats(self.h, C.byref(dry)))
-            self._plan[geo] = need
-        if need < 0:
-            raise bd.S2STHipError(f"workspace planning failed ({need})")
-        need = max(need, 64 << 20)
+        need = max(self._planned_floats(("enc", B, S), b), 64 << 20)
         self._grow_workspace(need, int(need * 1.05) + 4096)
         o = {"encoder_out": torch.empty(B, E, c.enc_dim, device=dev)}
         out = Outputs()
@@ -755,14 +745,7 @@ class Engine:
         c = self.cfg
         for b, _ in batches:
             b.training, b.want_attn = int(training), int(want_attn)
-            geo = (b.B, b.S, b.D, b.Ls, b.Lt, bool(b.tgt), b.training)
-            n = self._plan.get(geo)
-            if n is None:
-                n = int(self.lib.s2st_engine_workspace_floats(self.h, C.byref(b)))
-                self._plan[geo] = n
-            if n < 0:
-                raise bd.S2STHipError(f"workspace planning failed ({n})")
-            need = max(need, n)
+            need = max(need, self._planned_floats((b.B, b.S, b.D, b.Ls, b.Lt, bool(b.tgt), b.training), b))
             o = 2 * b.B * b.D * c.out_dim + b.B * b.D + 3 * b.B * b.E * c.enc_dim + b.B * b.E * b.D \
                 + b.B * b.Ls * c.src_vocab + b.B * b.Lt * c.tgt_vocab + b.B * b.E * c.src_vocab + 32
             out = max(out, o + 64 * 16)

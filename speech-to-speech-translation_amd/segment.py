@@ -18,7 +18,6 @@ in one call.
 from __future__ import annotations
 
 import argparse
-import os
 import sys
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -26,14 +25,15 @@ from typing import Dict, List, Optional
 import torch
 
 from . import segmentation as sgm
-from .translate import add_segment_flags, read_audio, segment_frames, segment_rows, write_pcm16, write_segments_tsv
+from .data.audio_utils import read_audio
+from .inference_common import default_device, write_pcm16
 
 
 def make_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="s2st_amd.segment", allow_abbrev=False)
     p.add_argument("audio", nargs="+", help="audio files; ids are the file stems")
     p.add_argument("--results-path", required=True)
-    add_segment_flags(p)
+    sgm.add_segment_flags(p)
     p.set_defaults(max_segment_s=30.0)  # (no model here: the limit of every recipe, 3000 frames)
     p.add_argument("--write-wavs", action="store_true", help="also write the trimmed segments as OUT/wav/<id>#<k>.wav")
     return p
@@ -41,14 +41,12 @@ def make_parser() -> argparse.ArgumentParser:
 
 def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None) -> Dict:
     args = make_parser().parse_args(argv)
-    opt = segment_frames(args, None)
+    opt = sgm.segment_frames(args, None)
     ids = [Path(f).stem for f in args.audio]
     if len(set(ids)) != len(ids):
         raise SystemExit(f"segment: duplicate ids {sorted({i for i in ids if ids.count(i) > 1})}")
     if args.segmenter == "device" and device is None:
-        if not torch.cuda.is_available():
-            raise SystemExit("s2st_amd.segment --segmenter device needs a HIP device (--segmenter host runs without one)")
-        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+        device = default_device("segment", needed_for="--segmenter device", without="--segmenter host")
     audio = [read_audio(f) for f in args.audio]
     segs: List = [None] * len(audio)
     for rate in sorted({r for _, r in audio}):
@@ -60,7 +58,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     out_root = Path(args.results_path)
     out_root.mkdir(exist_ok=True, parents=True)
     written = [str(out_root / "segments.tsv")]
-    write_segments_tsv(written[0], [r for i, s in zip(ids, segs) for r in segment_rows(i, s)])
+    sgm.write_segments_tsv(written[0], [r for i, s in zip(ids, segs) for r in sgm.segment_rows(i, s)])
     if args.write_wavs:
         (out_root / "wav").mkdir(exist_ok=True)
         for i, (w, rate), s in zip(ids, audio, segs):

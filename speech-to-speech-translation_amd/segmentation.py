@@ -31,7 +31,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -264,3 +264,64 @@ def segment(pcm_list: Sequence, rate: int, min_len: int, max_len: int, w: int = 
     if raw:  # (tests: the output arrays as the kernel left them, the rows behind nseg included)
         return res, {"nseg": nseg, "out": out, "cost": cost}
     return res
+
+
+# ---- the command-line side (translate --segment long, python -m s2st_amd.segment) ------------------------------------------
+def add_segment_flags(p) -> None:
+    """The segmentation's own flags on an argparse parser."""
+    a = p.add_argument
+    a("--max-segment-s", type=float, default=None, help="segments last this long at most (default: what the model takes)")
+    a("--min-segment-s", type=float, default=MIN_SEGMENT_S, help="... and this long at least")
+    a("--silence-db", type=float, default=SILENCE_DB,
+      help="a frame this far below the loudest frame's energy is silence (segments are trimmed to their speech)")
+    a("--cut-penalty-db", type=float, default=CUT_PENALTY_DB,
+      help="what one cut costs besides the energy it cuts through: the largest smoothed energy lowered by this")
+    a("--segment-pad-ms", type=float, default=PAD_MS, help="kept around a segment's first and last speech frame")
+    a("--segmenter", default="device", choices=["device", "host"],
+      help="s2st_segment_pcm16 on the device, or the same rules in numpy on the host (same files)")
+
+
+def segment_frames(args_or_opts, limit: Optional[int]) -> Dict:
+    """The flags in frames of 10 ms: {min_len, max_len, pad, silence_db, cut_penalty_db, segmenter}.  ``limit``: the
+    model's ``max_source_positions`` (None: no model)."""
+    g = (lambda k, d: args_or_opts.get(k, d)) if isinstance(args_or_opts, dict) else (lambda k, d: getattr(args_or_opts, k, d))
+    max_s = g("max_segment_s", None)
+    max_len = limit if max_s is None else int(round(float(max_s) * 100))
+    if max_len is None:
+        raise SystemExit("segment: --max-segment-s is needed without a model")
+    if limit is not None:
+        max_len = min(max_len, int(limit))
+    min_len = max(1, int(round(float(g("min_segment_s", MIN_SEGMENT_S)) * 100)))
+    if max_len < 2 * min_len:
+        raise SystemExit(f"segment: segments of at most {max_len} frames cannot all last {min_len} frames or more: "
+                         f"--max-segment-s must be at least twice --min-segment-s")
+    return {"min_len": min_len, "max_len": max_len, "pad": max(0, int(round(float(g("segment_pad_ms", PAD_MS)) / 10))),
+            "silence_db": float(g("silence_db", SILENCE_DB)), "cut_penalty_db": float(g("cut_penalty_db", CUT_PENALTY_DB)),
+            "segmenter": g("segmenter", "device")}
+
+
+SEGMENT_COLUMNS = ["id", "k", "src_start_s", "src_end_s", "trim_start_s", "trim_end_s", "dropped"]
+
+
+def segment_rows(name: str, seg, out_spans=None, out_rate: int = 0, text=None, n_text: int = 0) -> List[List[str]]:
+    """One row per segment of ``seg`` (SEGMENT_COLUMNS; times as ``%.6f`` seconds, which identify a sample at any audio
+    rate), then, with ``out_spans`` {k: (start, end)}, where its translation lies in the written wav (empty for a segment
+    that was not translated) and, with ``text`` {k: [strings]}, the text columns."""
+    rows = []
+    for k in range(len(seg)):
+        t = [f"{int(v) / seg.rate:.6f}" for v in (*seg.samples[k], *seg.trim_samples[k])]
+        row = [name, str(k)] + t + [str(int(seg.dropped[k]))]
+        if out_spans is not None:
+            row += [f"{v / out_rate:.6f}" for v in out_spans[k]] if k in out_spans else ["", ""]
+        if text is not None:
+            row += list(text.get(k, [""] * n_text))
+        rows.append(row)
+    return rows
+
+
+def write_segments_tsv(path: str, rows, out_columns: bool = False, text: Sequence[str] = ()) -> None:
+    head = SEGMENT_COLUMNS + (["out_start_s", "out_end_s"] if out_columns else []) + list(text)
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\t".join(head) + "\n")
+        for r in rows:
+            f.write("\t".join(r) + "\n")

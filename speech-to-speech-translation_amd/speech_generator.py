@@ -32,6 +32,16 @@ class PendingHypos(list):
         return self
 
 
+class _Chain:
+    """One decode chain of ``generate_many``: its step generator, stream, hypotheses and batch; ``alive`` until the generator
+    ends; ``held_at_post`` while its post-processing waits for the chain before it."""
+    __slots__ = ("steps", "stream", "hypos", "sample", "bsz", "alive", "held_at_post")
+
+    def __init__(self, steps, stream, hypos, sample, bsz):
+        self.steps, self.stream, self.hypos, self.sample, self.bsz = steps, stream, hypos, sample, bsz
+        self.alive, self.held_at_post = True, False
+
+
 class SpeechGenerator:
     def __init__(self, model, vocoder, data_cfg=None):
         self.model, self.vocoder = model, vocoder
@@ -58,7 +68,7 @@ class SpeechGenerator:
 
     # ``generate(..., defer_vocoder=True)``: the batch's vocoder launches go to a SECOND stream and the call returns a
     # ``PendingHypos`` -- the same list, whose "waveform" tensors are complete only after ``.wait()``.  A driver that calls
-    # ``generate`` for the next batch before it waits (generate_waveform.py, bench.py) gets the Griffin-Lim iterations of
+    # ``generate`` for the next batch before it waits (inference_common.drive, bench.py) gets the Griffin-Lim iterations of
     # batch k -- few large launches -- beside the decoding steps of batch k + 1 -- thousands of small dependent ones that
     # leave most of the chip idle.  Host-side order is unchanged (batch k's phase draws precede batch k + 1's), so are
     # the results.  Measured on the bench batch: 118.7 -> 111.7 ms per batch only -- the decoding steps under a running
@@ -104,10 +114,8 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
         self.max_iter, self.eos_prob_threshold, self.seed = max_iter, eos_prob_threshold, seed
         self.input_text = bool(input_text)
 
-    @torch.no_grad()
-    def generate(self, model, sample, has_targ: bool = False, **kwargs) -> List[Dict[str, Optional[torch.Tensor]]]:
-        model.eval()
-        eng = model.engine
+    def _begin(self, model, eng, sample) -> int:
+        """The encoder and the decoding caches of ``sample`` on ``eng``.  Returns the batch size."""
         ni = sample["net_input"]
         if self.input_text != bool(eng.cfg.text_input):
             # speech_generator_for_s2st.py:60-64 feeds token ids (--input-text true) or fbank frames to whatever encoder
@@ -119,8 +127,13 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
         else:
             src, src_lens = model._front_end(ni.get("src_speech"), ni.get("src_speech_lens"),
                                              ni.get("collated_audios_orig"), ni.get("padding_mask"))
-        bsz = src.shape[0]
-        self._enc = eng.decode_begin(src, src_lens, self.max_iter, speaker=sample.get("speaker"))
+        eng.decode_begin(src, src_lens, self.max_iter, speaker=sample.get("speaker"))
+        return src.shape[0]
+
+    @torch.no_grad()
+    def generate(self, model, sample, has_targ: bool = False, **kwargs) -> List[Dict[str, Optional[torch.Tensor]]]:
+        model.eval()
+        bsz = self._begin(model, model.engine, sample)
         self.defer_vocoder = bool(kwargs.get("defer_vocoder", False))
         finalized = PendingHypos(dict() for _ in range(bsz))
         try:
@@ -178,45 +191,35 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
         try:
             for eng, st, sample in zip(engs, streams, samples):
                 with torch.cuda.stream(st):
-                    ni = sample["net_input"]
-                    if self.input_text != bool(eng.cfg.text_input):
-                        raise ValueError("--input-text true goes with a text-input model (--arch t2s_transformer), and only with one")
-                    if self.input_text:
-                        src, src_lens = sample["src_text"], sample["src_text_len"]
-                    else:
-                        src, src_lens = model._front_end(ni.get("src_speech"), ni.get("src_speech_lens"),
-                                                         ni.get("collated_audios_orig"), ni.get("padding_mask"))
-                    bsz = src.shape[0]
-                    eng.decode_begin(src, src_lens, self.max_iter, speaker=sample.get("speaker"))
+                    bsz = self._begin(model, eng, sample)
                     fin = PendingHypos(dict() for _ in range(bsz))
-                    # [generator, stream, hypotheses, sample, batch size, alive, held at "post"]
-                    runs.append([self._decode_mel_steps(model, sample, bsz, fin, eng), st, fin, sample, bsz, True, False])
+                    runs.append(_Chain(self._decode_mel_steps(model, sample, bsz, fin, eng), st, fin, sample, bsz))
             alive = n
             while alive:
                 for k, r in enumerate(runs):
-                    if not r[5]:
+                    if not r.alive:
                         continue
-                    if r[6]:
-                        if runs[k - 1][5]:
+                    if r.held_at_post:
+                        if runs[k - 1].alive:
                             continue  # this batch's post-processing (its phase draws) comes after the previous batch's
-                        r[6] = False
-                    with torch.cuda.stream(r[1]):
+                        r.held_at_post = False
+                    with torch.cuda.stream(r.stream):
                         try:
-                            if next(r[0]) == "post" and k > 0:
-                                r[6] = True
+                            if next(r.steps) == "post" and k > 0:
+                                r.held_at_post = True
                         except StopIteration:
-                            r[5] = False
+                            r.alive = False
                             alive -= 1
                             if has_targ:
-                                self._add_targets(model, r[3], r[4], r[2])
+                                self._add_targets(model, r.sample, r.bsz, r.hypos)
             # the caller's stream takes in what the other chains produced
             for r in runs[1:]:
                 ev = torch.cuda.Event()
-                ev.record(r[1])
-                r[2]._events = tuple(r[2]._events) + (ev,)
+                ev.record(r.stream)
+                r.hypos._events = tuple(r.hypos._events) + (ev,)
         finally:
             self.defer_vocoder = False
-        return [r[2] for r in runs]
+        return [r.hypos for r in runs]
 
     def _generate_merged(self, model, samples, has_targ: bool = False, **kwargs):
         """Round 6: the batches of ``generate_many`` as ONE merged batch on ONE chain (<= 256 utterances: the skinny

@@ -38,11 +38,10 @@ out_end_s`` and the text columns.  The dumps are per segment (``id#k``).  A reco
 from __future__ import annotations
 
 import argparse
-import csv
+import functools
 import os
 import sys
 import time
-import wave
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -50,10 +49,12 @@ import numpy as np
 import torch
 
 from . import segmentation as sgm
-from .data import audio_utils
+from .data.audio_utils import read_audio, to_16bit_range
 from .data.feature_extraction import DeviceFeatureExtractor
 from .data.synthetic import batch_by_size
-from .generate_waveform import dump_result, load_task_model
+from .inference_common import (default_device, defer_vocoder, drive, dump_result, load_task_model, read_manifest,
+                               write_pcm16)
+from .models.wav2vec2_ctc import resample
 from .runtime import binding as bd
 from .runtime import streams as _streams
 from .tasks.s2s_translation import _flag_is_true
@@ -92,73 +93,13 @@ def make_parser() -> argparse.ArgumentParser:
     a("--dump-attentions", action="store_true")
     a("--dump-eos-probs", action="store_true")
     a("--precise-gemm", action="store_true", help="bf16x3 GEMMs (fp32-accurate; parity runs)")
-    add_segment_flags(p)
+    sgm.add_segment_flags(p)
     a("--segment", default="off", choices=["off", "long"],
       help="long: an input longer than the model takes is cut at its pauses (segmentation.py) and translated segment by "
            "segment; off: it is skipped")
     a("--max-pause-ms", type=float, default=sgm.MAX_PAUSE_MS,
       help="--segment long: the silence written between two segments' translations is the source pause, this long at most")
     return p
-
-
-def add_segment_flags(p: argparse.ArgumentParser) -> None:
-    """The segmentation's own flags (shared with ``python -m s2st_amd.segment``)."""
-    a = p.add_argument
-    a("--max-segment-s", type=float, default=None, help="segments last this long at most (default: what the model takes)")
-    a("--min-segment-s", type=float, default=sgm.MIN_SEGMENT_S, help="... and this long at least")
-    a("--silence-db", type=float, default=sgm.SILENCE_DB,
-      help="a frame this far below the loudest frame's energy is silence (segments are trimmed to their speech)")
-    a("--cut-penalty-db", type=float, default=sgm.CUT_PENALTY_DB,
-      help="what one cut costs besides the energy it cuts through: the largest smoothed energy lowered by this")
-    a("--segment-pad-ms", type=float, default=sgm.PAD_MS, help="kept around a segment's first and last speech frame")
-    a("--segmenter", default="device", choices=["device", "host"],
-      help="s2st_segment_pcm16 on the device, or the same rules in numpy on the host (same files)")
-
-
-def segment_frames(args_or_opts, limit: Optional[int]) -> Dict:
-    """The flags in frames of 10 ms: {min_len, max_len, pad, silence_db, cut_penalty_db, segmenter}.  ``limit``: the
-    model's ``max_source_positions`` (None: no model)."""
-    g = (lambda k, d: args_or_opts.get(k, d)) if isinstance(args_or_opts, dict) else (lambda k, d: getattr(args_or_opts, k, d))
-    max_s = g("max_segment_s", None)
-    max_len = limit if max_s is None else int(round(float(max_s) * 100))
-    if max_len is None:
-        raise SystemExit("segment: --max-segment-s is needed without a model")
-    if limit is not None:
-        max_len = min(max_len, int(limit))
-    min_len = max(1, int(round(float(g("min_segment_s", sgm.MIN_SEGMENT_S)) * 100)))
-    if max_len < 2 * min_len:
-        raise SystemExit(f"segment: segments of at most {max_len} frames cannot all last {min_len} frames or more: "
-                         f"--max-segment-s must be at least twice --min-segment-s")
-    return {"min_len": min_len, "max_len": max_len, "pad": max(0, int(round(float(g("segment_pad_ms", sgm.PAD_MS)) / 10))),
-            "silence_db": float(g("silence_db", sgm.SILENCE_DB)), "cut_penalty_db": float(g("cut_penalty_db", sgm.CUT_PENALTY_DB)),
-            "segmenter": g("segmenter", "device")}
-
-
-def write_pcm16(path: str, pcm: np.ndarray, sample_rate: int) -> None:
-    """16-bit PCM mono, the container ``generate_waveform.write_wav`` writes."""
-    with wave.open(path, "wb") as f:
-        f.setnchannels(1)
-        f.setsampwidth(2)
-        f.setframerate(int(sample_rate))
-        f.writeframes(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
-
-
-def read_audio(path: str) -> Tuple[np.ndarray, int]:
-    """``audio_utils.read_waveform`` + the mono mix-down of ``get_waveform``: float32 in [-1, 1) and the file's rate."""
-    wav, sr = audio_utils.get_waveform(path, normalization=True, mono=True, always_2d=False)
-    return np.ascontiguousarray(wav, dtype=np.float32), int(sr)
-
-
-def to_16bit_range(w: np.ndarray) -> np.ndarray:
-    """A waveform in [-1, 1) in Kaldi's 16-bit range, as stage 3 scales it (``x * 2**15`` in fp32): returned as int16 where
-    that is exactly what the samples are (decoded 16-bit PCM), else as float32."""
-    if w.dtype == np.int16:
-        return w
-    f = np.asarray(w, dtype=np.float32) * np.float32(2 ** 15)
-    if f.size and (np.abs(f).max() > 32768 or np.signbit(f[f == 0]).any()):
-        return f
-    i = np.clip(f, -32768, 32767).astype(np.int16)
-    return i if np.array_equal(i.astype(np.float32), f) else f
 
 
 def pcm16(waves: Sequence[torch.Tensor], device) -> List[np.ndarray]:
@@ -267,30 +208,31 @@ class SpeechTranslator:
         """The checkpoint's model on ``device`` with the generation-time flags of ``generate_waveform``; ``options``: the
         constructor's (src_sample_rate, output_sample_rate, text, beam, max_len_b, max_tokens, batch_size)."""
         if device is None:
-            if not torch.cuda.is_available():
-                raise SystemExit("s2st_amd.translate needs a HIP device (the product path has no CPU fallback)")
-            device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+            device = default_device("translate")
         largs = argparse.Namespace(data=data, config_yaml=config_yaml, path=path, task=task, precise_gemm=precise_gemm)
         trained = {}
-
-        def configure(margs):
-            # (refused before the model is built: a HuBERT front end would want its own weights)
-            if _flag_is_true(getattr(margs, "use_hubert", "false")):
-                raise SystemExit("translate: a --use-hubert model takes raw audio, not filter-bank features; the recipes "
-                                 "infer with --use-hubert False")
-            if _flag_is_true(getattr(margs, "input_text", "false")):
-                raise SystemExit("translate: the checkpoint is a text-input model (--input-text true): it has no speech to "
-                                 "translate")
-            trained["text_max_positions"] = getattr(margs, "max_target_positions", None)
-            margs.eos_prob_threshold = eos_prob_threshold
-            margs.spec_bwd_max_iter = spec_bwd_max_iter
-            margs.gl_phase_rng = "numpy"  # (the reference's draws, as generate_waveform's default)
-            margs.vocoder = vocoder
-            if max_target_positions is not None:
-                margs.max_target_positions = max_target_positions
-
+        configure = functools.partial(cls._configure, trained, vocoder, spec_bwd_max_iter, eos_prob_threshold,
+                                      max_target_positions)
         tk, model, margs = load_task_model(largs, device, configure, on_model_built)
         return cls(tk, model, margs, device, **dict(trained, **options))
+
+    @staticmethod
+    def _configure(trained, vocoder, spec_bwd_max_iter, eos_prob_threshold, max_target_positions, margs) -> None:
+        """The generation-time flags on the checkpoint's model flags; ``trained`` takes what the checkpoint carried."""
+        # (refused before the model is built: a HuBERT front end would want its own weights)
+        if _flag_is_true(getattr(margs, "use_hubert", "false")):
+            raise SystemExit("translate: a --use-hubert model takes raw audio, not filter-bank features; the recipes "
+                             "infer with --use-hubert False")
+        if _flag_is_true(getattr(margs, "input_text", "false")):
+            raise SystemExit("translate: the checkpoint is a text-input model (--input-text true): it has no speech to "
+                             "translate")
+        trained["text_max_positions"] = getattr(margs, "max_target_positions", None)
+        margs.eos_prob_threshold = eos_prob_threshold
+        margs.spec_bwd_max_iter = spec_bwd_max_iter
+        margs.gl_phase_rng = "numpy"  # (the reference's draws, as generate_waveform's default)
+        margs.vocoder = vocoder
+        if max_target_positions is not None:
+            margs.max_target_positions = max_target_positions
 
     # ---- the pipeline ---------------------------------------------------------------------------------------------------
     def _frames(self, n: int, rate: int) -> int:
@@ -307,7 +249,6 @@ class SpeechTranslator:
 
     def _front_end(self, waves, rates, rate: int):
         """One batch: (resample ->) 2**15 scale -> fbank_batch, in the stage's order.  Returns (src, frames) on the device."""
-        from .models.wav2vec2_ctc import resample
         scaled = [None] * len(waves)
         for r in sorted({r for r in rates if r != rate}):
             idx = [i for i, x in enumerate(rates) if x == r]
@@ -329,7 +270,7 @@ class SpeechTranslator:
         source rate, all such inputs in one call) and replaced, in place, by its trimmed segments that hold speech, as inputs
         ``id#k``.  Returns None when no input is that long, else the expanded (waves, rates, ids, speakers), ``origin``
         [(input, k or None)] per expanded position and ``groups`` {input: {"seg": Segmentation, "at": {k: position}}}."""
-        opt = segment_frames(self.segment_options, self.max_source_positions)
+        opt = sgm.segment_frames(self.segment_options, self.max_source_positions)
         long_ = [i for i in range(len(waves)) if n_frames[i] > opt["max_len"]]
         if not long_:
             return None
@@ -338,7 +279,6 @@ class SpeechTranslator:
             if rates[i] == rate:
                 src[i] = waves[i]
             else:  # resampled once, on the device; its segments then are inputs at the source rate
-                from .models.wav2vec2_ctc import resample
                 w = waves[i].astype(np.float32) / np.float32(32768) if waves[i].dtype == np.int16 else waves[i]
                 src[i] = resample([w], rates[i], rate, device=self.device)[0].cpu().numpy()
         shift, size = self.extractor._fbank_tables(rate, N_BINS)[:2]
@@ -390,58 +330,40 @@ class SpeechTranslator:
             out[which] = " ".join(h[which] for h in hyps)
         return out
 
-    def _run(self, audio, ids, speakers, sink, segment: Optional[str] = None) -> None:
-        """Translate ``audio`` [(samples, rate)]; ``sink(position, hypo)`` is called once per translated input."""
-        dev = self.device
-        self.skipped = []
-        self.segmentations = {}
-        self.seconds = {"front_end": 0.0, "generate": 0.0}
-        if len(audio) == 0:
-            return
-        rates = [int(r) for _, r in audio]
-        rate = self._source_rate(rates)
+    @staticmethod
+    def _normalise(audio) -> Tuple[List[np.ndarray], List[int]]:
+        """[(samples, rate)] -> mono int16 / float32 waveforms and their rates."""
         waves = []
         for w, _ in audio:
             w = np.asarray(w)
             if w.ndim != 1:
                 raise ValueError("translate takes mono waveforms (1-D arrays)")
             waves.append(w if w.dtype == np.int16 else np.ascontiguousarray(w, dtype=np.float32))
-        lens = [int(w.shape[0]) if r == rate else -(-int(w.shape[0]) * rate // r) for w, r in zip(waves, rates)]  # resample()'s
-        n_frames = np.array([self._frames(n, rate) for n in lens], dtype=np.int64)
-        mode = self.segment if segment is None else segment
-        if mode not in ("off", "long"):
-            raise ValueError(f"segment {mode!r}: expected 'off' or 'long'")
-        origin, groups, got, audio_ids = None, {}, {}, ids
-        expanded = self._segment_long(waves, rates, rate, n_frames, ids, speakers) if mode == "long" else None
-        if expanded is not None:
-            waves, rates, ids, speakers, origin, groups = expanded
-            lens = [int(w.shape[0]) for w in waves]  # (a segment is at the source rate; the others are as they were)
-            lens = [n if r == rate else -(-n * rate // r) for n, r in zip(lens, rates)]
-            n_frames = np.array([self._frames(n, rate) for n in lens], dtype=np.int64)
-            inner = sink
+        return waves, [int(r) for _, r in audio]
 
-            def sink(pos, hypo):  # a segment waits for its siblings; the input's joined result goes out with the last one
-                i, k = origin[pos]
-                if k is None:
-                    return inner(i, hypo)
-                got.setdefault(i, {})[k] = hypo
-                if len(got[i]) == groups[i]["expected"]:
-                    inner(i, self._join(audio_ids[i], groups[i], got.pop(i), rate))
-        spk_ids = None
-        if speakers is not None and any(s is not None for s in speakers):
-            table = self.task.speaker_to_id
-            if table is None:  # (as the dataset: without --speaker-to-id the speaker column is not read)
-                print("translate: the model was trained without --speaker-to-id: speakers are ignored", file=sys.stderr)
-            else:
-                for s in speakers:
-                    if s not in table:
-                        raise SystemExit(f"translate: unknown speaker {s!r} (the model knows {sorted(table)})")
-                spk_ids = [int(table[s]) for s in speakers]
-        # the dataset's order and batches: longest first, ties in input order (S2STDataset.ordered_indices), size filter, the
-        # native max-tokens batcher over frame counts (S2ST_TranslationTask.get_batch_iterator)
-        order = np.lexsort([np.arange(len(waves)), -n_frames])
+    def _frame_counts(self, waves, rates, rate: int) -> np.ndarray:
+        """Filter-bank frames per input at the source rate (an input at another rate: of resample()'s output length)."""
+        lens = [int(w.shape[0]) if r == rate else -(-int(w.shape[0]) * rate // r) for w, r in zip(waves, rates)]
+        return np.array([self._frames(n, rate) for n in lens], dtype=np.int64)
+
+    def _speaker_ids(self, speakers) -> Optional[List[int]]:
+        if speakers is None or all(s is None for s in speakers):
+            return None
+        table = self.task.speaker_to_id
+        if table is None:  # (as the dataset: without --speaker-to-id the speaker column is not read)
+            print("translate: the model was trained without --speaker-to-id: speakers are ignored", file=sys.stderr)
+            return None
+        for s in speakers:
+            if s not in table:
+                raise SystemExit(f"translate: unknown speaker {s!r} (the model knows {sorted(table)})")
+        return [int(table[s]) for s in speakers]
+
+    def _batches(self, ids, n_frames, groups, audio_ids) -> List:
+        """The dataset's order and batches: longest first, ties in input order (S2STDataset.ordered_indices), size filter,
+        the native max-tokens batcher over frame counts (S2ST_TranslationTask.get_batch_iterator).  What is left out goes
+        to ``skipped``; a segmented input (``groups``) learns how many of its segments to expect."""
         keep = []
-        for i in order:
+        for i in np.lexsort([np.arange(len(ids)), -n_frames]):
             if n_frames[i] == 0:
                 self.skipped.append((ids[i], "too short for one frame"))
             elif n_frames[i] > self.max_source_positions:
@@ -455,82 +377,78 @@ class SpeechTranslator:
         for i, why in self.skipped:
             print(f"translate: skipping {i}: {why}", file=sys.stderr)
         if not keep:
-            return
+            return []
         keep = np.asarray(keep, dtype=np.int64)
-        batches = batch_by_size(keep, n_frames[keep], self.max_tokens or 0, self.batch_size or -1, 1)
+        return batch_by_size(keep, n_frames[keep], self.max_tokens or 0, self.batch_size or -1, 1)
 
-        def samples():
-            for b in batches:
-                # (the collater's own sort of a batch, s2st_dataset.py:328-331: rows by descending length)
-                _, o = torch.tensor([int(n_frames[i]) for i in b], dtype=torch.long).sort(descending=True)
-                rows = [int(b[j]) for j in o.tolist()]
-                t0 = time.perf_counter()
-                src, frames = self._front_end([waves[i] for i in rows], [rates[i] for i in rows], rate)
-                self.seconds["front_end"] += time.perf_counter() - t0
-                speaker = None if spk_ids is None else torch.tensor([spk_ids[i] for i in rows], dtype=torch.long).view(-1, 1)
-                # (the lengths also as the host tensor the collater makes: the engine sizes its launches from them)
-                host_lens = torch.tensor([int(n_frames[i]) for i in rows], dtype=torch.long)
-                yield {"id": torch.tensor(rows, dtype=torch.long), "nsentences": len(rows), "speaker": speaker, "frames": frames,
-                       "net_input": {"src_speech": src, "src_speech_lens": host_lens, "speaker": speaker}}
-
-        def finish(sample, hypos):
-            if hasattr(hypos, "wait"):
-                hypos.wait()  # (the vocoder ran on the generator's second stream, beside the next batch's decoding)
-            outs = [h["waveform"] for h in hypos]
-            out_rate = self.sample_rate
-            if all(w is not None for w in outs):
-                if self.output_sample_rate not in (None, self.sample_rate):
-                    from .models.wav2vec2_ctc import resample
-                    out_rate = int(self.output_sample_rate)
-                    outs = resample(outs, self.sample_rate, out_rate, device=dev)
-                pcm = pcm16(outs, dev)
-            else:
-                pcm = [None] * len(outs)
-            for row, (i, hypo) in enumerate(zip(sample["id"].tolist(), hypos)):
-                hypo = dict(hypo, id=ids[i], pcm=pcm[row], sample_rate=out_rate,
-                            src_feature=sample["net_input"]["src_speech"][row, :int(n_frames[i])])
-                for which in self.heads:
-                    hypo[which] = sample["text"][which][row]
-                sink(i, hypo)
-
-        # driven as generate_waveform drives its generator: batch k's files are written after batch k + 1 has been enqueued
-        # (deferred vocoder), and several batches are decoded at once where the generator has that form
-        defer = dev.type == "cuda" and os.environ.get("S2ST_DEFER_VOCODER", "1") != "0"
-        chains = _streams.default_decode_chains() if (defer and hasattr(self.generator, "generate_many")) else 1
-        held, group = [], []
-
-        def flush():
-            nonlocal held, group
-            if not group:
-                return
+    def _samples(self, batches, waves, rates, rate: int, n_frames, spk_ids):
+        """The batches as collated samples: the front end, then the text heads' strings in ``sample["text"]``."""
+        for b in batches:
+            # (the collater's own sort of a batch, s2st_dataset.py:328-331: rows by descending length)
+            _, o = torch.tensor([int(n_frames[i]) for i in b], dtype=torch.long).sort(descending=True)
+            rows = [int(b[j]) for j in o.tolist()]
             t0 = time.perf_counter()
-            if len(group) >= 2:
-                hyps = list(self.generator.generate_many(self.model, group, has_targ=False, defer_vocoder=defer))
-            else:
-                hyps = [self.generator.generate(self.model, group[0], has_targ=False, defer_vocoder=defer)]
-            self.seconds["generate"] += time.perf_counter() - t0
-            for h in held:
-                finish(*h)
-            held = list(zip(group, hyps))
-            group = []
-            if not defer:
-                for h in held:
-                    finish(*h)
-                held = []
-
-        for sample in samples():
-            sample["text"] = {}
+            src, frames = self._front_end([waves[i] for i in rows], [rates[i] for i in rows], rate)
+            self.seconds["front_end"] += time.perf_counter() - t0
+            speaker = None if spk_ids is None else torch.tensor([spk_ids[i] for i in rows], dtype=torch.long).view(-1, 1)
+            # (the lengths also as the host tensor the collater makes: the engine sizes its launches from them)
+            host_lens = torch.tensor([int(n_frames[i]) for i in rows], dtype=torch.long)
+            sample = {"id": torch.tensor(rows, dtype=torch.long), "nsentences": len(rows), "speaker": speaker, "frames": frames,
+                      "net_input": {"src_speech": src, "src_speech_lens": host_lens, "speaker": speaker}, "text": {}}
             for which, gen in self.text_generators.items():
                 hyps = gen.generate([self.model], sample)
                 sample["text"][which] = [gen.tgt_dict.string(h[0]["tokens"].int().cpu()) for h in hyps]
-            group.append(sample)
-            if len(group) == chains:
-                flush()
-        flush()
-        for h in held:
-            finish(*h)
-        if dev.type == "cuda":
-            torch.cuda.synchronize(dev)
+            yield sample
+
+    def _finish(self, sink, ids, sample, hypos) -> None:
+        """A decoded batch: (resample ->) s2st_wave_to_pcm16, then ``sink(position, hypo)`` per utterance."""
+        if hasattr(hypos, "wait"):
+            hypos.wait()  # (the vocoder ran on the generator's second stream, beside the next batch's decoding)
+        outs = [h["waveform"] for h in hypos]
+        out_rate = self.sample_rate
+        if all(w is not None for w in outs):
+            if self.output_sample_rate not in (None, self.sample_rate):
+                out_rate = int(self.output_sample_rate)
+                outs = resample(outs, self.sample_rate, out_rate, device=self.device)
+            pcm = pcm16(outs, self.device)
+        else:
+            pcm = [None] * len(outs)
+        src, n_frames = sample["net_input"]["src_speech"], sample["net_input"]["src_speech_lens"].tolist()
+        for row, (i, hypo) in enumerate(zip(sample["id"].tolist(), hypos)):
+            hypo = dict(hypo, id=ids[i], pcm=pcm[row], sample_rate=out_rate, src_feature=src[row, :n_frames[row]])
+            for which in self.heads:
+                hypo[which] = sample["text"][which][row]
+            sink(i, hypo)
+
+    def _run(self, audio, ids, speakers, sink, segment: Optional[str] = None) -> None:
+        """Translate ``audio`` [(samples, rate)]; ``sink(position, hypo)`` is called once per translated input."""
+        dev = self.device
+        self.skipped = []
+        self.segmentations = {}
+        self.seconds = {"front_end": 0.0, "generate": 0.0}
+        if len(audio) == 0:
+            return
+        rate = self._source_rate([int(r) for _, r in audio])
+        waves, rates = self._normalise(audio)
+        n_frames = self._frame_counts(waves, rates, rate)
+        mode = self.segment if segment is None else segment
+        if mode not in ("off", "long"):
+            raise ValueError(f"segment {mode!r}: expected 'off' or 'long'")
+        groups, audio_ids = {}, ids
+        expanded = self._segment_long(waves, rates, rate, n_frames, ids, speakers) if mode == "long" else None
+        if expanded is not None:
+            waves, rates, ids, speakers, origin, groups = expanded
+            n_frames = self._frame_counts(waves, rates, rate)  # (a segment is at the source rate; the others are as they were)
+            sink = _Regroup(self, sink, origin, groups, audio_ids, rate)
+        spk_ids = self._speaker_ids(speakers)
+        batches = self._batches(ids, n_frames, groups, audio_ids)
+        # driven as generate_waveform drives its generator (inference_common.drive): batch k's files are written after batch
+        # k + 1 has been enqueued (deferred vocoder), and several batches are decoded at once where the generator has that form
+        defer = defer_vocoder(dev)
+        chains = _streams.default_decode_chains() if (defer and hasattr(self.generator, "generate_many")) else 1
+        self.seconds["generate"] = drive(self.generator, self.model, self._samples(batches, waves, rates, rate, n_frames, spk_ids),
+                                         functools.partial(self._finish, sink, ids), chains=chains, defer=defer,
+                                         sync_device=dev if dev.type == "cuda" else None)
 
     def translate(self, audio: Sequence[Tuple[np.ndarray, int]], ids: Optional[Sequence[str]] = None,
                   speakers: Optional[Sequence[Optional[str]]] = None, segment: Optional[str] = None) -> List[Optional[Dict]]:
@@ -545,51 +463,25 @@ class SpeechTranslator:
         if len(set(ids)) != len(ids):
             raise SystemExit(f"translate: duplicate ids {sorted({i for i in ids if ids.count(i) > 1})}")
         out: List[Optional[Dict]] = [None] * len(audio)
-
-        def sink(i, hypo):
-            out[i] = hypo
-
-        self._run(audio, ids, speakers, sink, segment)
+        self._run(audio, ids, speakers, out.__setitem__, segment)
         return out
 
 
-SEGMENT_COLUMNS = ["id", "k", "src_start_s", "src_end_s", "trim_start_s", "trim_end_s", "dropped"]
+class _Regroup:
+    """The sink of a call with segmented inputs: a segment waits for its siblings; the input's joined result goes out with the
+    last one.  ``origin``: [(input, k or None)] per expanded position; ``groups``: ``SpeechTranslator._segment_long``'s."""
 
+    def __init__(self, translator, sink, origin, groups, ids, rate):
+        self.translator, self.sink, self.origin, self.groups, self.ids, self.rate = translator, sink, origin, groups, ids, rate
+        self.got: Dict[int, Dict[int, Dict]] = {}
 
-def segment_rows(name: str, seg, out_spans=None, out_rate: int = 0, text=None, n_text: int = 0) -> List[List[str]]:
-    """One row per segment of ``seg`` (SEGMENT_COLUMNS; times as ``%.6f`` seconds, which identify a sample at any audio
-    rate), then, with ``out_spans`` {k: (start, end)}, where its translation lies in the written wav (empty for a segment
-    that was not translated) and, with ``text`` {k: [strings]}, the text columns."""
-    rows = []
-    for k in range(len(seg)):
-        t = [f"{int(v) / seg.rate:.6f}" for v in (*seg.samples[k], *seg.trim_samples[k])]
-        row = [name, str(k)] + t + [str(int(seg.dropped[k]))]
-        if out_spans is not None:
-            row += [f"{v / out_rate:.6f}" for v in out_spans[k]] if k in out_spans else ["", ""]
-        if text is not None:
-            row += list(text.get(k, [""] * n_text))
-        rows.append(row)
-    return rows
-
-
-def write_segments_tsv(path: str, rows, out_columns: bool = False, text: Sequence[str] = ()) -> None:
-    head = SEGMENT_COLUMNS + (["out_start_s", "out_end_s"] if out_columns else []) + list(text)
-    with open(path, "w", encoding="utf-8") as f:
-        f.write("\t".join(head) + "\n")
-        for r in rows:
-            f.write("\t".join(r) + "\n")
-
-
-def read_manifest(path: str) -> Tuple[List[str], List[str], Optional[List[str]]]:
-    with open(path) as f:
-        rows = list(csv.DictReader(f, delimiter="\t", quotechar=None, doublequote=False, lineterminator="\n",
-                                   quoting=csv.QUOTE_NONE))
-    if not rows or "id" not in rows[0] or "audio" not in rows[0]:
-        raise SystemExit(f"translate: {path} must be a TSV with the columns id, audio and optionally speaker")
-    root = Path(path).parent
-    files = [r["audio"] if os.path.isabs(r["audio"]) or os.path.exists(r["audio"]) else (root / r["audio"]).as_posix()
-             for r in rows]
-    return [r["id"] for r in rows], files, ([r["speaker"] for r in rows] if "speaker" in rows[0] else None)
+    def __call__(self, pos, hypo):
+        i, k = self.origin[pos]
+        if k is None:
+            return self.sink(i, hypo)
+        self.got.setdefault(i, {})[k] = hypo
+        if len(self.got[i]) == self.groups[i]["expected"]:
+            self.sink(i, self.translator._join(self.ids[i], self.groups[i], self.got.pop(i), self.rate))
 
 
 def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None, on_model_built=None) -> Dict:
@@ -616,7 +508,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         silence_db=args.silence_db, cut_penalty_db=args.cut_penalty_db, segment_pad_ms=args.segment_pad_ms,
         segmenter=args.segmenter)
     if args.segment == "long":
-        segment_frames(tr.segment_options, tr.max_source_positions)  # (a contradiction among the flags is refused up front)
+        sgm.segment_frames(tr.segment_options, tr.max_source_positions)  # (a contradiction among the flags is refused up front)
     audio = [read_audio(f) for f in files]
     if args.seed is not None:
         np.random.seed(args.seed)
@@ -641,7 +533,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
                 dump_result(dargs, args.vocoder, out_rate, h["id"], h, written)
                 n_frames += int(h["feature"].shape[0])
             text = {k: [h[which] for which in tr.heads] for k, h in zip(hypo["segment_ids"], hypo["segments"])}
-            seg_rows[i] = segment_rows(ids[i], hypo["segmentation"], hypo["out_spans"], out_rate, text, len(tr.heads))
+            seg_rows[i] = sgm.segment_rows(ids[i], hypo["segmentation"], hypo["out_spans"], out_rate, text, len(tr.heads))
         else:
             dump_result(dargs, args.vocoder, out_rate, ids[i], hypo, written)
             n_frames += int(hypo["feature"].shape[0])
@@ -665,9 +557,9 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     if args.segment == "long":
         for i, seg in tr.segmentations.items():  # (a recording none of whose segments was translated keeps its rows)
             if i not in seg_rows:
-                seg_rows[i] = segment_rows(ids[i], seg, {}, out_rate, {}, len(tr.heads))
+                seg_rows[i] = sgm.segment_rows(ids[i], seg, {}, out_rate, {}, len(tr.heads))
         path = str(out_root / "segments.tsv")
-        write_segments_tsv(path, [r for i in sorted(seg_rows) for r in seg_rows[i]], out_columns=True, text=list(tr.heads))
+        sgm.write_segments_tsv(path, [r for i in sorted(seg_rows) for r in seg_rows[i]], out_columns=True, text=list(tr.heads))
         written.append(path)
     return {"utterances": n_utt, "mel_frames": n_frames, "seconds": seconds, "front_end_seconds": tr.seconds["front_end"],
             "files": written, "sample_rate": out_rate, "skipped": [i for i, _ in tr.skipped],
