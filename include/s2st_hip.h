@@ -926,6 +926,35 @@ int s2st_segment_pcm16(const int16_t* pcm, const int64_t* soff, int32_t B, int32
                        void* stream);
 
 /* ======================================================================================
+ * Time-scale modification of 16-bit PCM (csrc/time_scale.hip): the tempo of speech changes, its pitch does not -- what fits
+ * a translated segment to the room it has on the source's time line.  The reference has NO counterpart, so the definition is
+ * this library's own; time_scale.host_time_scale restates it in numpy and the two agree bit for bit.  Waveform-similarity
+ * overlap-add on integers, no table and no floating point:
+ *   x = recording b's samples pcm[in_off[b] .. in_off[b + 1]), n >= 0 of them; x[t] = 0 for every read outside [0, n);
+ *   m = out_off[b + 1] - out_off[b] >= 0, the output length;  N = the frame length (even),  Hs = N / 2,  D = the search radius;
+ *   cross-fade weights  wr[i] = ((2 i + 1) 32768) / N  (floor),  wf[i] = 32768 - wr[i],  i in [0, Hs);
+ *   the output is built in J = ceil(m / Hs) hops and only its first m samples are written:
+ *   hop 0:       p_0 = 0,  out[i] = x[i];
+ *   hop j >= 1:  nominal position  a_j = floor(j Hs n / m)  (64-bit);
+ *                template          tpl[i] = x[p_{j-1} + Hs + i], the natural continuation of what was written last;
+ *                candidates        every c in [a_j - D, a_j + D];
+ *                cost(c)           = sum_{i < Hs} |x[c + i] - tpl[i]|  (exact in int32: Hs <= 2048);
+ *                p_j               = the candidate of least cost; TIES GO TO THE SMALLEST |c - a_j|, THEN TO THE SMALLER c;
+ *                out[j Hs + i]     = (x[p_j + i] wr[i] + tpl[i] wf[i] + 16384) >> 15  (arithmetic shift).
+ * Consequences: m == n gives x back byte for byte; |p_j - a_j| <= D; a signal of exact period P <= D with Hs >= P comes out as
+ * the same periodic signal while the templates lie inside the recording: a hop then costs nothing and copies its template, so
+ * for m >= n every hop j with a_{j-1} + D + 2 Hs <= n is exact (up to a ratio of 1.5 that was all but the last Hs + D samples in
+ * every case tried; at 2 it is not).  The definition is total: any n, any m.
+ * Needs 2 <= N <= 4096 even, 0 <= D <= 2048, B >= 0: S2ST_ERR_ARG otherwise, and nothing is launched (B = 0: returns 0).
+ * Outputs: out, int16, recording b's m samples at out_off[b]; pos, int32, p_0 .. p_{J-1} of recording b at pos_off[b] (hops
+ * beyond pos_off[b + 1] - pos_off[b] are not recorded).  One launch, one workgroup per recording (hop j needs p_{j-1}; the
+ * candidates and the terms of a cost are parallel within the hop), no atomics, nothing read back to the host, stream-ordered;
+ * results repeat bit for bit and do not depend on the batch a recording is in.
+ * ====================================================================================== */
+int s2st_time_scale_pcm16(const int16_t* pcm, const int64_t* in_off, const int64_t* out_off, int32_t B, int32_t N, int32_t D,
+                          int16_t* out, int32_t* pos, const int64_t* pos_off, void* stream);
+
+/* ======================================================================================
  * Gradient exchange: SUM all-reduce over an RCCL communicator, one process per GPU.  Replaces the bucketed NCCL
  * all-reduce torch DDP runs for the reference (fairseq/models/distributed_fairseq_model.py:58-67); the trainer hands
  * over contiguous ranges of the flat gradient arena as the backward finishes them (s2st_engine_segment_range) and

@@ -408,6 +408,9 @@ int64_t s2st_segment_workspace(int32_t B, int32_t Tmax, int32_t min_len) { retur
 int s2st_segment_pcm16(const int16_t* pcm, const int64_t* soff, int32_t B, int32_t Tmax, int32_t win, int32_t hop, int32_t w, int32_t min_len, int32_t max_len, int32_t pad, double penalty_factor, double silence_factor, int32_t Kcap, int32_t* nseg, int32_t* seg_start, int32_t* seg_end, int32_t* trim_start, int32_t* trim_end, int32_t* dropped, int64_t* cost, void* workspace, int64_t workspace_bytes, void* stream) {
   return s2st_segment_speech(pcm, soff, B, Tmax, win, hop, w, min_len, max_len, pad, penalty_factor, silence_factor, Kcap, nseg, seg_start, seg_end, trim_start, trim_end, dropped, cost, workspace, workspace_bytes, (hipStream_t)stream);
 }
+int s2st_time_scale_pcm16(const int16_t* pcm, const int64_t* in_off, const int64_t* out_off, int32_t B, int32_t N, int32_t D, int16_t* out, int32_t* pos, const int64_t* pos_off, void* stream) {
+  return s2st_time_scale_wsola(pcm, in_off, out_off, B, N, D, out, pos, pos_off, (hipStream_t)stream);
+}
 #ifndef S2ST_SOURCE_HASH
 #define S2ST_SOURCE_HASH "unknown"  // (__graft_entry__.build passes the hash of the sources; the test emulator build does not)
 #endif

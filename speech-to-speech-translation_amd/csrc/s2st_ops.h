@@ -366,6 +366,13 @@ int s2st_segment_speech(const int16_t* pcm, const int64_t* soff, int B, int Tmax
                         int64_t workspace_bytes, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// Time-scale modification of 16-bit PCM (time_scale.hip; the definition is in include/s2st_hip.h): waveform-similarity
+// overlap-add on integers over a ragged batch, one workgroup per recording walking its hops
+// ---------------------------------------------------------------------------------------
+int s2st_time_scale_wsola(const int16_t* pcm, const int64_t* in_off, const int64_t* out_off, int B, int N, int D, int16_t* out,
+                          int* pos, const int64_t* pos_off, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh
 // ---------------------------------------------------------------------------------------
 // y[b][q up + r][o] = epilogue(bias[o] + sum_{c, j} in[b][q + off[r] + j dil][c] * w[r][o][j][c]) for q < nq; input rows

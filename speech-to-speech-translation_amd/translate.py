@@ -2,7 +2,8 @@
 
     python -m s2st_amd.translate DATA --config-yaml config.yaml --path CKPT.pt --results-path OUT \
         (--inputs A.wav B.wav ... | --manifest FILE.tsv) [--src-sample-rate R] [--output-sample-rate R] [--speaker NAME] \
-        [--text none|asr|st|both] [--beam 5] [--max-tokens N | --batch-size N] [--vocoder griffin_lim|hifigan] ...
+        [--text none|asr|st|both] [--beam 5] [--max-tokens N | --batch-size N] [--vocoder griffin_lim|hifigan] \
+        [--segment long [--timeline joined|source] [--max-tempo 1.25]] [--tempo 1.0] [--time-scaler device|host] ...
 
 The reference has no such script: its ``generate_waveform.py`` walks a split of a stage-3 data directory (features read
 from a zip through a TSV manifest).  This one joins the pieces that exist into a device-resident path for NEW recordings:
@@ -34,6 +35,16 @@ trimmed spans -- ``asr.txt`` / ``st.txt`` one line per recording (the segments' 
 ``OUT/segments.tsv`` one row per segment: ``id, k, src_start_s, src_end_s, trim_start_s, trim_end_s, dropped, out_start_s,
 out_end_s`` and the text columns.  The dumps are per segment (``id#k``).  A recording without any speech is skipped and listed.
 **Parity unpinned: the reference has no segmentation.**
+
+``--tempo F`` (default 1.0: nothing is called) changes the tempo of what was generated without changing its pitch (time_scale.py:
+waveform-similarity overlap-add on integers, csrc/time_scale.hip or with ``--time-scaler host`` in numpy, bit-equal): an output
+of ``n`` samples -- an uncut input's, or each segment's of a cut one -- becomes ``ceil(n * 1000 / round(1000 F))`` long.
+``--timeline source`` (needs ``--segment long``; default ``joined``: the above) lays a cut recording's segments out on the
+SOURCE's time line instead: segment k starts where its trimmed span started in the source (in output samples), is compressed --
+by ``--max-tempo`` at most -- when its translation is longer than the room up to the next segment, and pushes the next one
+when even that is not enough (``time_scale.place``); zeros lie wherever no segment does, the wav is at least as long as the
+recording, and ``segments.tsv`` gains a last column ``tempo`` (natural length / placed length).  An input that was not cut is
+written as before.  **Parity unpinned: the reference has no time-scale modification.**
 """
 from __future__ import annotations
 
@@ -49,6 +60,7 @@ import numpy as np
 import torch
 
 from . import segmentation as sgm
+from . import time_scale as tsm
 from .data.audio_utils import read_audio, to_16bit_range
 from .data.feature_extraction import DeviceFeatureExtractor
 from .data.synthetic import batch_by_size
@@ -99,7 +111,31 @@ def make_parser() -> argparse.ArgumentParser:
            "segment; off: it is skipped")
     a("--max-pause-ms", type=float, default=sgm.MAX_PAUSE_MS,
       help="--segment long: the silence written between two segments' translations is the source pause, this long at most")
+    tsm.add_time_scale_flags(p)
+    a("--timeline", default="joined", choices=["joined", "source"],
+      help="joined: a cut recording's translated segments follow each other with the pauses of --max-pause-ms; source (needs "
+           "--segment long): each starts where it started in the source and is compressed to the room it has there.  It "
+           "applies to recordings that were cut: an input that was not cut is written as before")
+    a("--max-tempo", type=float, default=tsm.MAX_TEMPO,
+      help="--timeline source: a segment is compressed by this factor at most (then it runs over and pushes the next one); a "
+           "design choice, not a measurement; must be >= --tempo")
     return p
+
+
+def check_tempo(tempo: float, max_tempo: float, timeline: str, segment: str) -> Tuple[int, int]:
+    """(tempo, max tempo) in thousandths, or ValueError: the tempo within what ``time_scale`` takes, the limit not below it,
+    ``timeline="source"`` only with ``segment="long"``."""
+    if timeline not in ("joined", "source"):
+        raise ValueError(f"timeline {timeline!r}: expected 'joined' or 'source'")
+    if timeline == "source" and segment != "long":
+        raise ValueError("--timeline source needs --segment long: it places the segments of a recording that was cut")
+    t, mt = tsm.tempo_milli(tempo), tsm.tempo_milli(max_tempo)
+    lo, hi = int(1000 * tsm.MIN_RATIO), int(1000 * tsm.MAX_RATIO)
+    if not lo <= t <= hi:
+        raise ValueError(f"--tempo {tempo} is outside [{tsm.MIN_RATIO}, {tsm.MAX_RATIO}]")
+    if mt < t or mt > hi:
+        raise ValueError(f"--max-tempo {max_tempo} must be at least --tempo {tempo} and at most {tsm.MAX_RATIO}")
+    return t, mt
 
 
 def pcm16(waves: Sequence[torch.Tensor], device) -> List[np.ndarray]:
@@ -128,7 +164,8 @@ class SpeechTranslator:
                  output_sample_rate: Optional[int] = None, text: str = "none", beam: int = 5,
                  max_tokens: Optional[int] = None, batch_size: Optional[int] = None,
                  max_len_b: int = 200, text_max_positions: Optional[int] = None, cmvn=None, segment: str = "off",
-                 max_pause_ms: float = sgm.MAX_PAUSE_MS, **segment_options):
+                 max_pause_ms: float = sgm.MAX_PAUSE_MS, tempo: float = 1.0, timeline: str = "joined",
+                 max_tempo: float = tsm.MAX_TEMPO, time_scaler: str = "device", **segment_options):
         """``cmvn``: (mean, std) fp32 [80] instead of the data config's source statistics (a model built without a data
         directory: tools/translate_rate.py)."""
         eng = model.engine
@@ -171,6 +208,12 @@ class SpeechTranslator:
             raise TypeError(f"SpeechTranslator: unknown options {sorted(unknown)}")
         self.segment, self.max_pause_ms, self.segment_options = segment, float(max_pause_ms), dict(segment_options)
         self.segmentations: Dict[int, sgm.Segmentation] = {}  # of the last call: {input position: its segmentation}
+        # --tempo / --timeline source (time_scale.py)
+        if time_scaler not in ("device", "host"):
+            raise ValueError(f"time_scaler {time_scaler!r}: expected 'device' or 'host'")
+        self.tempo_milli, self.max_tempo_milli = check_tempo(tempo, max_tempo, timeline, segment)
+        self.timeline, self.time_scaler = timeline, time_scaler
+        self._natural: set = set()  # of the running call: the expanded positions whose PCM keeps its length until it is placed
 
     # ---- construction ---------------------------------------------------------------------------------------------------
     @staticmethod
@@ -330,6 +373,43 @@ class SpeechTranslator:
             out[which] = " ".join(h[which] for h in hyps)
         return out
 
+    def _scale(self, pcm: Sequence[np.ndarray], out_lens: Sequence[int], rate: int) -> List[np.ndarray]:
+        """``pcm[b]`` at ``out_lens[b]`` samples: those whose length changes in ONE ``time_scale`` call, the others as they are."""
+        idx = [b for b, (p, m) in enumerate(zip(pcm, out_lens)) if int(m) != len(p)]
+        out = list(pcm)
+        if idx:
+            t0 = time.perf_counter()
+            res = tsm.time_scale([pcm[b] for b in idx], [int(out_lens[b]) for b in idx], rate=rate, device=self.device,
+                                 scaler=self.time_scaler)
+            self.seconds["time_scale"] = self.seconds.get("time_scale", 0.0) + time.perf_counter() - t0
+            for b, (y, _) in zip(idx, res):
+                out[b] = y
+        return out
+
+    def _join_source(self, name, group, got, rate):
+        """The result of a segmented input under ``timeline="source"``: every segment starts where its trimmed span started in
+        the source, as long as ``time_scale.place`` allows it to be (all segments whose length changes go to the device in
+        one call); zeros wherever no segment lies; at least as long as the source.  ``tempo``: {k: natural / placed length}."""
+        seg, ks = group["seg"], sorted(got)
+        hyps = [got[k] for k in ks]
+        out_rate = int(hyps[0]["sample_rate"])
+        out = {"id": name, "segments": hyps, "segment_ids": ks, "segmentation": seg, "pcm": None, "sample_rate": out_rate,
+               "src_rate": int(rate), "out_spans": {}, "tempo": {}}
+        if all(h["pcm"] is not None for h in hyps):
+            total = -(-int(seg.n_samples) * out_rate // int(rate))
+            starts = [int(seg.trim_samples[k][0]) * out_rate // int(rate) for k in ks]
+            natural = [int(len(h["pcm"])) for h in hyps]
+            at, lens = tsm.place(starts, natural, total, self.tempo_milli, self.max_tempo_milli)
+            pcm = np.zeros(max([total] + [a + m for a, m in zip(at, lens)]), np.int16)
+            for k, a, m, n, y in zip(ks, at, lens, natural, self._scale([h["pcm"] for h in hyps], lens, out_rate)):
+                pcm[a:a + m] = y
+                out["out_spans"][k] = (a, a + m)
+                out["tempo"][k] = n / m if m else 1.0
+            out["pcm"] = pcm
+        for which in self.heads:
+            out[which] = " ".join(h[which] for h in hyps)
+        return out
+
     @staticmethod
     def _normalise(audio) -> Tuple[List[np.ndarray], List[int]]:
         """[(samples, rate)] -> mono int16 / float32 waveforms and their rates."""
@@ -411,6 +491,10 @@ class SpeechTranslator:
                 out_rate = int(self.output_sample_rate)
                 outs = resample(outs, self.sample_rate, out_rate, device=self.device)
             pcm = pcm16(outs, self.device)
+            if self.tempo_milli != 1000:  # (a segment that --timeline source places keeps its length until then)
+                rows = sample["id"].tolist()
+                pcm = self._scale(pcm, [len(p) if i in self._natural else tsm.scaled_len(len(p), self.tempo_milli)
+                                        for i, p in zip(rows, pcm)], out_rate)
         else:
             pcm = [None] * len(outs)
         src, n_frames = sample["net_input"]["src_speech"], sample["net_input"]["src_speech_lens"].tolist()
@@ -420,11 +504,12 @@ class SpeechTranslator:
                 hypo[which] = sample["text"][which][row]
             sink(i, hypo)
 
-    def _run(self, audio, ids, speakers, sink, segment: Optional[str] = None) -> None:
+    def _run(self, audio, ids, speakers, sink, segment: Optional[str] = None, timeline: Optional[str] = None) -> None:
         """Translate ``audio`` [(samples, rate)]; ``sink(position, hypo)`` is called once per translated input."""
         dev = self.device
         self.skipped = []
         self.segmentations = {}
+        self._natural = set()
         self.seconds = {"front_end": 0.0, "generate": 0.0}
         if len(audio) == 0:
             return
@@ -434,12 +519,16 @@ class SpeechTranslator:
         mode = self.segment if segment is None else segment
         if mode not in ("off", "long"):
             raise ValueError(f"segment {mode!r}: expected 'off' or 'long'")
+        line = self.timeline if timeline is None else timeline
+        check_tempo(self.tempo_milli / 1000, self.max_tempo_milli / 1000, line, mode)
         groups, audio_ids = {}, ids
         expanded = self._segment_long(waves, rates, rate, n_frames, ids, speakers) if mode == "long" else None
         if expanded is not None:
             waves, rates, ids, speakers, origin, groups = expanded
             n_frames = self._frame_counts(waves, rates, rate)  # (a segment is at the source rate; the others are as they were)
-            sink = _Regroup(self, sink, origin, groups, audio_ids, rate)
+            sink = _Regroup(self, sink, origin, groups, audio_ids, rate, line)
+            if line == "source":
+                self._natural = {pos for pos, (_, k) in enumerate(origin) if k is not None}
         spk_ids = self._speaker_ids(speakers)
         batches = self._batches(ids, n_frames, groups, audio_ids)
         # driven as generate_waveform drives its generator (inference_common.drive): batch k's files are written after batch
@@ -451,19 +540,23 @@ class SpeechTranslator:
                                          sync_device=dev if dev.type == "cuda" else None)
 
     def translate(self, audio: Sequence[Tuple[np.ndarray, int]], ids: Optional[Sequence[str]] = None,
-                  speakers: Optional[Sequence[Optional[str]]] = None, segment: Optional[str] = None) -> List[Optional[Dict]]:
+                  speakers: Optional[Sequence[Optional[str]]] = None, segment: Optional[str] = None,
+                  timeline: Optional[str] = None) -> List[Optional[Dict]]:
         """``audio``: [(samples, rate)] -- mono float waveforms in [-1, 1), or int16 PCM.  Returns one entry per input, in
         input order (``None`` for a skipped one).  ``segment`` ("off" / "long"; default: the constructor's): with "long" an
         input longer than the model takes is cut at its pauses and its entry is ``{"id", "segments": the hypotheses of its
         segments ``id#k`` in order, "segment_ids": their k, "segmentation", "pcm": their PCM joined with the pauses between
-        them, "sample_rate", "src_rate", "out_spans": {k: (start, end) in pcm}}`` plus the joined ``asr`` / ``st`` strings."""
+        them, "sample_rate", "src_rate", "out_spans": {k: (start, end) in pcm}}`` plus the joined ``asr`` / ``st`` strings.
+        ``timeline`` ("joined" / "source"; default: the constructor's): with "source" (needs "long") that entry's ``pcm`` has
+        the segments where they were in the source (``_join_source``), ``out_spans`` says where, and ``tempo`` {k: natural /
+        placed length} how much each was compressed; the segments' own ``pcm`` stay as generated."""
         ids = [str(i) for i in ids] if ids is not None else [str(i) for i in range(len(audio))]
         if len(ids) != len(audio) or (speakers is not None and len(speakers) != len(audio)):
             raise ValueError("translate: ids / speakers must have one entry per input")
         if len(set(ids)) != len(ids):
             raise SystemExit(f"translate: duplicate ids {sorted({i for i in ids if ids.count(i) > 1})}")
         out: List[Optional[Dict]] = [None] * len(audio)
-        self._run(audio, ids, speakers, out.__setitem__, segment)
+        self._run(audio, ids, speakers, out.__setitem__, segment, timeline)
         return out
 
 
@@ -471,8 +564,9 @@ class _Regroup:
     """The sink of a call with segmented inputs: a segment waits for its siblings; the input's joined result goes out with the
     last one.  ``origin``: [(input, k or None)] per expanded position; ``groups``: ``SpeechTranslator._segment_long``'s."""
 
-    def __init__(self, translator, sink, origin, groups, ids, rate):
+    def __init__(self, translator, sink, origin, groups, ids, rate, timeline="joined"):
         self.translator, self.sink, self.origin, self.groups, self.ids, self.rate = translator, sink, origin, groups, ids, rate
+        self.join = translator._join_source if timeline == "source" else translator._join
         self.got: Dict[int, Dict[int, Dict]] = {}
 
     def __call__(self, pos, hypo):
@@ -481,7 +575,7 @@ class _Regroup:
             return self.sink(i, hypo)
         self.got.setdefault(i, {})[k] = hypo
         if len(self.got[i]) == self.groups[i]["expected"]:
-            self.sink(i, self.translator._join(self.ids[i], self.groups[i], self.got.pop(i), self.rate))
+            self.sink(i, self.join(self.ids[i], self.groups[i], self.got.pop(i), self.rate))
 
 
 def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None, on_model_built=None) -> Dict:
@@ -494,6 +588,10 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     if len(set(ids)) != len(ids):
         raise SystemExit(f"translate: duplicate ids {sorted({i for i in ids if ids.count(i) > 1})}: two inputs would be written "
                          f"to the same file")
+    try:
+        check_tempo(args.tempo, args.max_tempo, args.timeline, args.segment)  # (refused before the model is loaded)
+    except ValueError as e:
+        raise SystemExit(f"translate: {e}")
     if speakers is None and args.speaker is not None:
         speakers = [args.speaker] * len(files)
     elif speakers is not None:
@@ -506,7 +604,8 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
         text=args.text, beam=args.beam, max_len_b=args.max_len_b, max_tokens=args.max_tokens, batch_size=args.batch_size,
         segment=args.segment, max_pause_ms=args.max_pause_ms, max_segment_s=args.max_segment_s, min_segment_s=args.min_segment_s,
         silence_db=args.silence_db, cut_penalty_db=args.cut_penalty_db, segment_pad_ms=args.segment_pad_ms,
-        segmenter=args.segmenter)
+        segmenter=args.segmenter, tempo=args.tempo, timeline=args.timeline, max_tempo=args.max_tempo,
+        time_scaler=args.time_scaler)
     if args.segment == "long":
         sgm.segment_frames(tr.segment_options, tr.max_source_positions)  # (a contradiction among the flags is refused up front)
     audio = [read_audio(f) for f in files]
@@ -525,6 +624,7 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     n_utt = n_frames = 0
 
     seg_rows: Dict[int, List[List[str]]] = {}
+    tsv_text = list(tr.heads) + (["tempo"] if args.timeline == "source" else [])  # (the columns behind out_end_s)
 
     def sink(i, hypo):
         nonlocal n_utt, n_frames
@@ -533,7 +633,10 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
                 dump_result(dargs, args.vocoder, out_rate, h["id"], h, written)
                 n_frames += int(h["feature"].shape[0])
             text = {k: [h[which] for which in tr.heads] for k, h in zip(hypo["segment_ids"], hypo["segments"])}
-            seg_rows[i] = sgm.segment_rows(ids[i], hypo["segmentation"], hypo["out_spans"], out_rate, text, len(tr.heads))
+            if args.timeline == "source":
+                for k in text:
+                    text[k].append(f"{hypo['tempo'][k]:.6f}" if k in hypo["tempo"] else "")
+            seg_rows[i] = sgm.segment_rows(ids[i], hypo["segmentation"], hypo["out_spans"], out_rate, text, len(tsv_text))
         else:
             dump_result(dargs, args.vocoder, out_rate, ids[i], hypo, written)
             n_frames += int(hypo["feature"].shape[0])
@@ -557,9 +660,9 @@ def main(argv: Optional[List[str]] = None, device: Optional[torch.device] = None
     if args.segment == "long":
         for i, seg in tr.segmentations.items():  # (a recording none of whose segments was translated keeps its rows)
             if i not in seg_rows:
-                seg_rows[i] = sgm.segment_rows(ids[i], seg, {}, out_rate, {}, len(tr.heads))
+                seg_rows[i] = sgm.segment_rows(ids[i], seg, {}, out_rate, {}, len(tsv_text))
         path = str(out_root / "segments.tsv")
-        sgm.write_segments_tsv(path, [r for i in sorted(seg_rows) for r in seg_rows[i]], out_columns=True, text=list(tr.heads))
+        sgm.write_segments_tsv(path, [r for i in sorted(seg_rows) for r in seg_rows[i]], out_columns=True, text=tsv_text)
         written.append(path)
     return {"utterances": n_utt, "mel_frames": n_frames, "seconds": seconds, "front_end_seconds": tr.seconds["front_end"],
             "files": written, "sample_rate": out_rate, "skipped": [i for i, _ in tr.skipped],
