@@ -592,10 +592,6 @@ int s2st_argmax_dim1_f32(const float* x, int64_t* idx, int32_t B, int32_t E, int
 int s2st_affine_cols_f32(const float* x, const float* scale, const float* shift, float* y, int64_t rows, int32_t C, void* stream);
 int s2st_exp_transpose_f32(const float* x, float* y, int32_t T, int32_t C, void* stream);
 int s2st_clamp_min_f32(float* x, int64_t n, float lo, void* stream);
-int s2st_gl_polar_f32(const float* mag, const float* ang, float* X, int32_t F, int32_t T, void* stream);
-int s2st_gl_project_f32(const float* mag, const float* Y, float* X, int32_t F, int32_t T, void* stream);
-int s2st_reflect_pad_f32(const float* x, float* y, int32_t n, int32_t pad, void* stream);
-int s2st_gl_overlap_add_f32(const float* frames, const float* wsq, float* wave, int32_t T, int32_t n_fft, int32_t hop, int32_t n_out, void* stream);
 
 /* Batched Griffin-Lim on the bf16 matrix cores (vocoder.py:100-123 for every utterance of a batch at once):
  * U utterances of tl[u] <= Tmax frames, rows r = u * Tmax + t.  fp32 rows are stored for the GEMM as bf16
@@ -708,11 +704,13 @@ int s2st_ln_gemm_skinny_f32(const float* x, int64_t ldx, const float* ln_gamma, 
 int64_t s2st_batch_by_size(const int64_t* num_tokens, int64_t n, int64_t max_tokens, int64_t max_sentences, int32_t bsz_mult, int32_t* batch_ends);
 
 /* MCD evaluation (examples/s2s_trans/tasks/s2s_translation.py:414-552): batched DTW over the padded
- * [B][M][N] distance tensor (shapes [B][2] = (m, n) per element, or NULL), RMS feature distance, MFCC glue */
+ * [B][M][N] distance tensor (shapes [B][2] = (m, n) per element, or NULL), RMS feature distance, MFCC glue
+ * (s2st_reflect_pad_f32: y[i] = x[reflect(i - pad)], n + 2 * pad samples: the STFT's padding, n > pad) */
 int s2st_dtw_f32(const float* dist, const int32_t* shapes, int32_t B, int32_t M, int32_t N, float* cumdist, int32_t* backptr, int32_t* pathmap, void* stream);
 int s2st_rms_dist_f32(const float* x1, const float* x2, float* out, int32_t m, int32_t n, int32_t D, int64_t ldo, void* stream);
 int s2st_power_spec_f32(const float* Y, float* P, int32_t T, int32_t F, void* stream);
 int s2st_log_offset_f32(float* x, int64_t n, float eps, void* stream);
+int s2st_reflect_pad_f32(const float* x, float* y, int32_t n, int32_t pad, void* stream);
 
 /* Aux ASR (which = 0) / ST (which = 1) text decoder, forward only, over an encoder tap: what the reference runs
  * when fairseq_cli/generate_for_s2st.py:107-111 swaps model.decoder for model.aux_{asr,st}_decoder and

@@ -235,18 +235,6 @@ int s2st_exp_transpose_f32(const float* x, float* y, int32_t T, int32_t C, void*
   return s2st_exp_transpose(x, y, T, C, (hipStream_t)stream);
 }
 int s2st_clamp_min_f32(float* x, int64_t n, float lo, void* stream) { return s2st_clamp_min(x, n, lo, (hipStream_t)stream); }
-int s2st_gl_polar_f32(const float* mag, const float* ang, float* X, int32_t F, int32_t T, void* stream) {
-  return s2st_gl_polar(mag, ang, X, F, T, (hipStream_t)stream);
-}
-int s2st_gl_project_f32(const float* mag, const float* Y, float* X, int32_t F, int32_t T, void* stream) {
-  return s2st_gl_project(mag, Y, X, F, T, (hipStream_t)stream);
-}
-int s2st_reflect_pad_f32(const float* x, float* y, int32_t n, int32_t pad, void* stream) {
-  return s2st_reflect_pad(x, y, n, pad, (hipStream_t)stream);
-}
-int s2st_gl_overlap_add_f32(const float* frames, const float* wsq, float* wave, int32_t T, int32_t n_fft, int32_t hop, int32_t n_out, void* stream) {
-  return s2st_gl_overlap_add(frames, wsq, wave, T, n_fft, hop, n_out, (hipStream_t)stream);
-}
 
 int s2st_dtw_f32(const float* dist, const int32_t* shapes, int32_t B, int32_t M, int32_t N, float* cumdist, int32_t* backptr, int32_t* pathmap, void* stream) {
   return s2st_dtw(dist, shapes, B, M, N, cumdist, backptr, pathmap, (hipStream_t)stream);
@@ -256,6 +244,9 @@ int s2st_rms_dist_f32(const float* x1, const float* x2, float* out, int32_t m, i
 }
 int s2st_power_spec_f32(const float* Y, float* P, int32_t T, int32_t F, void* stream) { return s2st_power_spec(Y, P, T, F, (hipStream_t)stream); }
 int s2st_log_offset_f32(float* x, int64_t n, float eps, void* stream) { return s2st_log_offset(x, n, eps, (hipStream_t)stream); }
+int s2st_reflect_pad_f32(const float* x, float* y, int32_t n, int32_t pad, void* stream) {
+  return s2st_reflect_pad(x, y, n, pad, (hipStream_t)stream);
+}
 
 int s2st_gl_polar_split_f32(const float* mag, const float* aux, int32_t from_spectrum, const int32_t* tl, void* Xs, int32_t U, int32_t F, int32_t Fp, int32_t Tmax, void* stream) {
   return s2st_gl_polar_split(mag, aux, from_spectrum, tl, (uint16_t*)Xs, U, F, Fp, Tmax, (hipStream_t)stream);

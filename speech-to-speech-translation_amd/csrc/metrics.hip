@@ -93,6 +93,17 @@ __global__ __launch_bounds__(256) void log_offset_kernel(float* __restrict__ x, 
   if (i < n) x[i] = logf(x[i] + eps);
 }
 
+// reflect-pad a waveform by `pad` on both sides: y[i] = x[reflect(i - pad)]
+__global__ __launch_bounds__(256) void reflect_pad_kernel(const float* __restrict__ x, float* __restrict__ y, int n,
+                                                          int pad) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)n + 2 * pad) return;
+  int j = (int)i - pad;
+  if (j < 0) j = -j;
+  if (j >= n) j = 2 * (n - 1) - j;
+  y[i] = x[j];
+}
+
 }  // namespace
 
 int s2st_dtw(const float* dist, const int* shapes, int B, int M, int N, float* cum, int* backptr, int* pathmap,
@@ -119,5 +130,12 @@ int s2st_power_spec(const float* Y, float* P, int T, int F, hipStream_t st) {
 int s2st_log_offset(float* x, long n, float eps, hipStream_t st) {
   if (n <= 0) return 0;
   S2ST_LAUNCH(log_offset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, eps);
+  return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
+}
+
+int s2st_reflect_pad(const float* x, float* y, int n, int pad, hipStream_t st) {
+  if (n <= pad) return S2ST_ERR_SHAPE;
+  const long m = (long)n + 2 * pad;
+  S2ST_LAUNCH(reflect_pad_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, x, y, n, pad);
   return hipGetLastError() == hipSuccess ? 0 : S2ST_ERR_LAUNCH;
 }

@@ -397,7 +397,7 @@ int s2st_hifigan_post(const float* x, const float* w, const float* bias, float* 
                       int B, int L, int C, int k, float slope, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
-// inference (infer.hip): incremental-decoding attention, stop / alignment / de-CMVN helpers, Griffin-Lim
+// inference: incremental-decoding attention, stop / alignment / de-CMVN helpers (decode.hip)
 // ---------------------------------------------------------------------------------------
 int s2st_decode_attn(const float* q, long ldq, float* kc, float* vc, long ldk, long kbs, const int* klen,
                      int nkeys, int B, int H, int dh, float scale, float* o, long ldo, float* attn_mean, int S,
@@ -418,18 +418,16 @@ int s2st_decode_replay_commit(int* step, uint64_t* seeds, const float* cur_feat,
 int s2st_sigmoid(const float* x, float* y, long n, hipStream_t st);
 int s2st_argmax_dim1(const float* x, long* idx, int B, int E, int D, hipStream_t st);
 int s2st_affine_cols(const float* x, const float* scale, const float* shift, float* y, long rows, int C, hipStream_t st);
+// Griffin-Lim vocoder (griffin_lim.hip): log-mel -> magnitude glue, the dense-DFT form's pieces around the bf16 GEMMs
 int s2st_exp_transpose(const float* x, float* y, int T, int C, hipStream_t st);
 int s2st_clamp_min(float* x, long n, float lo, hipStream_t st);
-int s2st_gl_polar(const float* mag, const float* ang, float* X, int F, int T, hipStream_t st);
-int s2st_gl_project(const float* mag, const float* Y, float* X, int F, int T, hipStream_t st);
-int s2st_reflect_pad(const float* x, float* y, int n, int pad, hipStream_t st);
 int s2st_gl_polar_split(const float* mag, const float* aux, int from_spectrum, const int* tl, uint16_t* Xs, int U, int F,
                         int Fp, int Tmax, hipStream_t st);
 int s2st_gl_frame_split(const float* wave, const int* tl, uint16_t* As, int U, int Tmax, int hop, int n_fft, int Lw,
                         hipStream_t st);
 int s2st_gl_overlap_add_b(const float* frames, const float* wsq_all, const long* wsq_off, const int* tl, float* wave,
                           int U, int Tmax, int n_fft, int hop, int Lw, hipStream_t st);
-// FFT-based Griffin-Lim (infer.hip): n_fft a power of two in 256 ... 2048 (s2st_gl_fft_supported) or one of the mixed-radix
+// FFT-based Griffin-Lim (griffin_lim.hip): n_fft a power of two in 256 ... 2048 (s2st_gl_fft_supported) or one of the mixed-radix
 // sizes 240 / 400 / 1200 (s2st_fft_len_supported: both lists, fft_lds.h); X is complex [U * Tmax][n_fft / 2 + 1] (re, im
 // interleaved); win [n_fft]; tw [n_fft] complex = exp(-2 pi i j / n_fft)
 bool s2st_gl_fft_supported(int n_fft);
@@ -446,8 +444,6 @@ int s2st_gl_istft_ola(const float* X, const int* tl, const float* win, const flo
                       float* wave, int U, int Tmax, int n_fft, int hop, int Lw, hipStream_t st);
 int s2st_gl_istft_frames(const float* X, const int* tl, const float* win, const float* tw, float* frames, int U, int Tmax,
                          int n_fft, int hop, hipStream_t st);
-int s2st_gl_overlap_add(const float* frames, const float* wsq, float* wave, int T, int n_fft, int hop, int n_out,
-                        hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // MCD evaluation (metrics.hip)
@@ -457,6 +453,7 @@ int s2st_dtw(const float* dist, const int* shapes, int B, int M, int N, float* c
 int s2st_rms_dist(const float* x1, const float* x2, float* out, int m, int n, int D, long ldo, hipStream_t st);
 int s2st_power_spec(const float* Y, float* P, int T, int F, hipStream_t st);
 int s2st_log_offset(float* x, long n, float eps, hipStream_t st);
+int s2st_reflect_pad(const float* x, float* y, int n, int pad, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // losses (losses.hip)

@@ -157,7 +157,7 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
         workspace, bf16 copies) and its own stream; the host alternates the step loops.  Results and their order are those
         of ``generate`` called on the batches one after the other: a batch's post-processing -- its vocoder's draws from
         numpy's phase stream -- is held until the batch before it has done its own, and its run-ahead phase stream starts
-        from the state the earlier batch's draws REALLY leave numpy in (vocoder._HostMTStream).  Returns the hypothesis lists
+        from the state the earlier batch's draws REALLY leave numpy in (phase_streams._HostMTStream).  Returns the hypothesis lists
         (``PendingHypos``) in batch order."""
         model.eval()
         samples = list(samples)

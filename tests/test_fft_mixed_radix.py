@@ -1,5 +1,5 @@
 """The mixed-radix LDS FFT sizes (csrc/fft_lds.h: 240 = 8 * 6 * 5, 400 = 8 * 2 * 5 * 5, 1200 = 8 * 6 * 5 * 5) under the
-Griffin-Lim kernels (csrc/infer.hip) and the log-mel extraction (csrc/features.hip).  1200 / 1024 / 300 at 24 kHz is the geometry
+Griffin-Lim kernels (csrc/griffin_lim.hip) and the log-mel extraction (csrc/features.hip).  1200 / 1024 / 300 at 24 kHz is the geometry
 stage 3 writes into config.yaml, so it is what ``generate_waveform`` and ``--eval-inference`` run on a directory this
 package prepared.
 

@@ -330,6 +330,14 @@ def test_vocoder_against_reference_wrapper(backend, golden_dir):
         ref = z[f"spec.{u}"]
         assert float(np.abs(spec.cpu().numpy() - ref).max()) < 2e-5 * float(np.abs(ref).max())
         assert float(spec.min()) >= 0.0
+    # the same through the vocoder's own padded-batch inversion (what __call__ and batch run): frame-major rows
+    Ts, mag = voc._magnitudes(feats)
+    backend.sync()
+    assert Ts == lens and tuple(mag.shape) == (len(lens), max(lens), voc.F)
+    for u, T in enumerate(lens):
+        ref = z[f"spec.{u}"].T
+        assert float(np.abs(mag[u, :T].cpu().numpy() - ref).max()) < 2e-5 * float(np.abs(ref).max())
+        assert float(mag[u, :T].min()) >= 0.0
 
 
 def test_mcd_against_reference_wrapper(backend, golden_dir):
@@ -410,7 +418,7 @@ def test_generate_waveform_harness_on_disk_corpus(backend, tmp_path):
 
 
 def _gl_numpy_fft(spec, angles, n_fft, win_length, hop, n_iter):
-    """Griffin-Lim in float64 with numpy's real FFTs -- the form csrc/infer.hip computes.  That this IS the reference's
+    """Griffin-Lim in float64 with numpy's real FFTs -- the form csrc/griffin_lim.hip computes.  That this IS the reference's
     arithmetic (dense Fourier-basis convolutions, audio_utils.py:226-271 / vocoder.py:56-98) is what
     test_fourier_bases_are_real_ffts pins; the reference golden at n_fft 256 pins the kernels themselves."""
     Fq, T = spec.shape
@@ -523,6 +531,97 @@ def test_fft_griffin_lim_kernels(backend, golden_dir, monkeypatch, n_fft, win, h
         backend.sync()
         scale = float(np.abs(ref).max())
         assert e_fft < 2e-4 * scale and e_dense < 2e-3 * scale, (e_fft / scale, e_dense / scale)
+
+
+def test_dense_griffin_lim_without_fft_plan(backend):
+    """An n_fft the LDS FFT kernels have no plan for: the dense bf16x3 GEMM form, which a single utterance takes as a batch
+    of one.  Ragged batch with the shortest utterance the reference's reflect padding is defined for, against the float64
+    numpy form to the 2e-3 of the waveform scale this form is held to at the golden's geometry."""
+    V = importlib.import_module(PKG + ".vocoder")
+    n_fft, win, hop, n_iter = 128, 100, 32, 2
+    assert not backend.bd.lib().s2st_fft_len_supported_i32(n_fft)
+    T_min = n_fft // (2 * hop) + 2
+    assert hop * (T_min - 1) > n_fft // 2 >= hop * (T_min - 2)
+    rs = np.random.RandomState(n_fft)
+    Fq = n_fft // 2 + 1
+    specs = [np.abs(rs.randn(Fq, t)).astype(np.float32) for t in (T_min, 11)]
+    angs = [IO.initial_angles((Fq, s.shape[1]), rs) for s in specs]
+    gl = V.GriffinLim(n_fft, win, hop, n_iter, backend.device)
+    assert not gl.use_fft
+    many = gl.batch([torch.from_numpy(s) for s in specs], angs)
+    for s, a, w in zip(specs, angs, many):
+        ref = _gl_numpy_fft(s, a, n_fft, win, hop, n_iter)
+        one = gl(torch.from_numpy(s), a)
+        alone = gl.batch([torch.from_numpy(s)], [a])[0]
+        backend.sync()
+        scale = float(np.abs(ref).max())
+        errs = [float(np.abs(x.cpu().numpy() - ref).max()) / scale for x in (w, one)]
+        print("dense", (n_fft, win, hop), s.shape, "batch / call error of the waveform scale:", errs)
+        assert w.shape[0] == one.shape[0] == ref.shape[0]
+        assert max(errs) < 2e-3, errs
+        assert torch.equal(one, alone)
+
+
+def test_phase_source_alone(monkeypatch):
+    """phase_streams.PhaseSource on the host (no device): the draws of a batch announced with ``prefetch`` are the ones
+    sequential ``np.random.rand(F, T)`` calls give, and numpy's global generator ends where they leave it -- whether the
+    run-ahead stream serves them or declines (too few drawn ahead, somebody else used the generator) -- for two batches
+    pending at once, and after a prefetch that nobody draws from."""
+    P = importlib.import_module(PKG + ".phase_streams")
+    monkeypatch.delenv("S2ST_GL_PHASE_STREAM", raising=False)
+    Fq, dev = 7, torch.device("cpu")
+
+    def plain(Ts):
+        return np.concatenate([np.random.rand(Fq, T).reshape(-1) for T in Ts])
+
+    def drawn(src, Ts):
+        uni, uoff = src.draw(Ts)
+        assert uni.dtype == torch.float64 and uoff.dtype == torch.int64
+        assert uoff.tolist() == [Fq * sum(Ts[:u]) for u in range(len(Ts))]
+        return uni.numpy().copy()
+
+    Ts, Ts2 = [5, 3, 9], [4, 6]
+    n = Fq * sum(Ts)
+    np.random.seed(11)
+    want, want2, tail = plain(Ts), plain(Ts2), np.random.rand(2)
+    np.random.seed(11)
+    assert np.array_equal(drawn(P.PhaseSource(dev, Fq), Ts), want)  # no prefetch at all
+    for upper, served in ((n + 50, True), (n, True), (n - 1, False)):
+        src = P.PhaseSource(dev, Fq)
+        np.random.seed(11)
+        src.prefetch(upper)
+        got = drawn(src, Ts)
+        assert np.array_equal(got, want), upper
+        assert (src._pin is None) == served, upper  # (the staging buffer of the ordinary draws exists only after a fall-back)
+        assert np.array_equal(plain(Ts2), want2) and np.array_equal(np.random.rand(2), tail), upper
+    # two batches pending: the second stream starts where the first one's draws REALLY end, not at its upper bound
+    src = P.PhaseSource(dev, Fq)
+    np.random.seed(11)
+    src.prefetch(n + 100)
+    src.prefetch(Fq * sum(Ts2) + 30)
+    assert np.array_equal(drawn(src, Ts), want) and np.array_equal(drawn(src, Ts2), want2)
+    assert src._pin is None and np.array_equal(np.random.rand(2), tail)
+    # a prefetch nobody draws from is abandoned when a third one arrives (two may be pending); the two behind it decline
+    src = P.PhaseSource(dev, Fq)
+    np.random.seed(11)
+    src.prefetch(1000)
+    first = src._pending[0]
+    src.prefetch(n + 100)
+    src.prefetch(Fq * sum(Ts2) + 30)
+    first.thread.join(timeout=30.0)
+    assert not first.thread.is_alive() and first.taken.is_set() and first not in src._pending
+    assert np.array_equal(drawn(src, Ts), want) and np.array_equal(drawn(src, Ts2), want2)
+    assert np.array_equal(np.random.rand(2), tail)
+    # somebody else draws between prefetch and draw: the run-ahead declines, the result is the plain draw from there
+    np.random.seed(11)
+    np.random.rand(1)
+    want_d, tail_d = plain(Ts), np.random.rand(2)
+    src = P.PhaseSource(dev, Fq)
+    np.random.seed(11)
+    src.prefetch(n + 50)
+    np.random.rand(1)
+    assert np.array_equal(drawn(src, Ts), want_d) and src._pin is not None
+    assert np.array_equal(np.random.rand(2), tail_d)
 
 
 def test_initial_phases_numpy_stream_and_device_generator(backend):
