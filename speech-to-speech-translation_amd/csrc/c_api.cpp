@@ -402,6 +402,10 @@ int s2st_segment_pcm16(const int16_t* pcm, const int64_t* soff, int32_t B, int32
 int s2st_time_scale_pcm16(const int16_t* pcm, const int64_t* in_off, const int64_t* out_off, int32_t B, int32_t N, int32_t D, int16_t* out, int32_t* pos, const int64_t* pos_off, void* stream) {
   return s2st_time_scale_wsola(pcm, in_off, out_off, B, N, D, out, pos, pos_off, (hipStream_t)stream);
 }
+int64_t s2st_reseg_workspace(int32_t B, int32_t Nmax, int32_t Mmax, int32_t Kmax) { return s2st_reseg_ws_bytes(B, Nmax, Mmax, Kmax); }
+int s2st_reseg_i32(const int32_t* hyp, const int64_t* hoff, const int32_t* ref, const int64_t* roff, const int32_t* ends, const int64_t* eoff, int32_t B, int32_t Nmax, int32_t Mmax, int32_t Kmax, int32_t* cuts, int32_t* seg_dist, int32_t* dist, void* workspace, int64_t workspace_bytes, void* stream) {
+  return s2st_reseg_align(hyp, hoff, ref, roff, ends, eoff, B, Nmax, Mmax, Kmax, cuts, seg_dist, dist, workspace, workspace_bytes, (hipStream_t)stream);
+}
 #ifndef S2ST_SOURCE_HASH
 #define S2ST_SOURCE_HASH "unknown"  // (__graft_entry__.build passes the hash of the sources; the test emulator build does not)
 #endif

@@ -373,6 +373,16 @@ int s2st_time_scale_wsola(const int16_t* pcm, const int64_t* in_off, const int64
                           int* pos, const int64_t* pos_off, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// Minimum-error re-segmentation (reseg.hip; the definition is in include/s2st_hip.h): the Levenshtein alignment of a
+// document's hypothesis to its concatenated reference sentences and the cuts where it crosses the sentence boundaries, over
+// a ragged batch, one workgroup per document walking the table as a skewed wavefront
+// ---------------------------------------------------------------------------------------
+int64_t s2st_reseg_ws_bytes(int B, int Nmax, int Mmax, int Kmax);
+int s2st_reseg_align(const int* hyp, const int64_t* hoff, const int* ref, const int64_t* roff, const int* ends,
+                     const int64_t* eoff, int B, int Nmax, int Mmax, int Kmax, int* cuts, int* seg_dist, int* dist,
+                     void* workspace, int64_t workspace_bytes, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // HiFi-GAN generator (hifigan.hip): implicit-GEMM dilated / polyphase transposed conv1d, conv_post + tanh
 // ---------------------------------------------------------------------------------------
 // y[b][q up + r][o] = epilogue(bias[o] + sum_{c, j} in[b][q + off[r] + j dil][c] * w[r][o][j][c]) for q < nq; input rows
