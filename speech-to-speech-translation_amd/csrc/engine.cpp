@@ -1,318 +1,14 @@
-// s2st training engine: forward + loss + backward of the s2st_transformer as one stream-ordered
-// schedule of HIP kernels over flat parameter / gradient arenas and a bump-allocated
-// activation workspace.  No tracing compiler, no autograd graph: the forward pushes one
-// backward closure per op on a tape; the backward pops them.  Parameters are laid out in
-// forward-use order so the backward finishes gradient ranges back-to-front, which lets the
-// host overlap RCCL all-reduce of finished ranges with the rest of the backward.
-//
-// Reference behaviour reproduced (file:line under /root/reference):
-//   encoder   examples/s2s_trans/models/s2st_transformer.py:94-140, 195-237
-//   decoder   s2st_transformer.py:369-456 ; Prenet/Postnet fairseq/models/text_to_speech/tacotron2.py:85-126
-//   layers    fairseq/modules/transformer_layer.py:107-165, 301-446 ; MHA multihead_attention.py:160-385
-//   aux text decoders  s2st_transformer.py:483-578 ; transformer_decoder.py:253-378
-//   criterion examples/s2s_trans/criterions/s2st_loss.py:179-315
-// Layout: activations are [B][T][C] row-major (the reference is [T][B][C]); padded rows are
-// computed exactly as the reference computes them.
-#include <cmath>
+// engine.cpp -- the extern "C" surface of the engine (include/s2st_hip.h: s2st_engine_*, s2st_hubert_*, s2st_w2v_ctc_*,
+// s2st_hifigan_*) and the helpers only it uses.  The engine itself: engine.h and the engine_*.cpp units.
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <string>
 #include <vector>
 
-#include "s2st_ops.h"
-#include <hip/hip_ext.h>
+#include "engine.h"
 
-namespace {
-
-struct PInfo {
-  std::string name;
-  long off, numel;
-  int ndim;
-  int shape[4];
-  int is_buffer;
-};
-
-struct Ten {  // plain [rows][cols] fp32 activation
-  float* d = nullptr;
-  float* g = nullptr;
-  // fast (bf16-operand) mode: bf16 copies of d / g with row stride hld(), made by the producer
-  // kernel when it can, else by a cast kernel at the first GEMM that reads them
-  bf16raw* h = nullptr;
-  bf16raw* gh = nullptr;
-  int rows = 0, cols = 0;
-  bool needs_grad = true;
-  bool want_gh = false;  // the gradient is consumed as a GEMM operand: its producer writes gh too
-  bool gh_only = false;  // ... and ONLY as that operand (fused attention's O): the producer writes no fp32 gradient (g stays allocated, unwritten)
-  // output of conv() whose data gradient reads a bf16 halo image [B][Th][O] (rows at pad + stride * t, zeros elsewhere):
-  // the closure that produces this tensor's gradient (BatchNorm / GLU backward) writes the image itself and leaves it in
-  // gimg; conv()'s closure then skips its own image pass
-  bool img_want = false;
-  int img_B = 0, img_Tout = 0, img_Th = 0, img_pad = 0, img_stride = 1;
-  bf16raw* gimg = nullptr;
-  bool resid_in_loss = false;  // post-net output: the loss root already added this gradient into feat's (post = feat + postnet(feat))
-  // produced by linear(act = ReLU, dropout p) with a single consumer (FFN hidden): the consumer's
-  // data-gradient GEMM applies the activation backward + bias gradient in its epilogue and leaves the
-  // ready bf16 operand in gpre_h (no fp32 gradient of this tensor is ever written)
-  int act_mode = 0;
-  float act_p = 0.f;
-  long act_bias = -1;
-  // produced by linear(no activation, dropout p) [+ residual]: the layer norm that consumes it first (hence last
-  // in the backward, when its gradient is complete) emits the bf16 operand dropout'(g) + bias gradient (gpre_h)
-  bool drop2_ok = false, ln_seen = false;
-  float drop2_p = 0.f;
-  uint64_t drop2_seed = 0;
-  long drop2_bias = -1;
-  bool lin_plain = false;  // output of a bias-only linear (no activation / dropout / residual): its gradient IS the GEMM operand
-  bf16raw* gpre_h = nullptr;
-  long n() const { return (long)rows * cols; }
-  int hld() const { return (cols + 7) & ~7; }
-};
-
-struct LinP { long w, b; int N, K; };           // offsets into the param arena (b < 0: no bias)
-struct LNP { long g, b; int C; };
-struct AttnP { long kvq_w, kvq_b, out_w, out_b; };                 // self: [3C][C] k,v,q rows
-struct XAttnP { long kv_w, kv_b, q_w, q_b, out_w, out_b; };         // cross: kv [2C][Cenc]
-struct EncLayerP { AttnP sa; LNP ln1; LinP fc1, fc2; LNP ln2; };
-struct DecLayerP { AttnP sa; LNP ln1; XAttnP xa; LNP ln2; LinP fc1, fc2; LNP ln3; };
-struct ConvP { long w, b; int O, I, Kw; };
-struct BNP { long g, b, rm, rv; int C; };
-struct AuxP {
-  long embed; int V, in_dim, d, layers, out_dim;
-  long proj_in;  // -1 if none
-  std::vector<DecLayerP> L;
-  LNP ln; bool has_ln;
-  long proj_out; // -1 if none
-  long out_proj;
-};
-
-}  // namespace
-
-struct s2st_engine {
-  s2st_model_config c;
-  std::vector<PInfo> infos;
-  long n_params = 0, n_buffers = 0;
-  float *P = nullptr, *G = nullptr, *BUF = nullptr;
-  // weight-gradient GEMMs are off the backward critical path: they run on a second stream, next
-  // to the data-gradient chain (each of these GEMMs alone fills about half of the 256 CUs)
-  hipStream_t side_ = nullptr;
-  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_taps_ = nullptr;
-  bool overlap_aux = true;  // S2ST_NO_AUX_OVERLAP=1 (A/B switch)
-  bool hoist_kv = true;     // S2ST_NO_KV_HOIST=1 (A/B switch): cross-attention K|V projections inside the layers
-  hipEvent_t ev_kv_ = nullptr;
-  bool kv_wait_ = false;    // the data path has not yet waited for the hoisted K|V projections
-  hipEvent_t ev_auxb_ = nullptr;
-  size_t aux_wait_idx = 0, aux_lo_idx = 0, aux_hi_idx = 0;  // tape indices: tap-LN end; aux section [lo, hi)
-  bool aux_bwd_on_side = false;
-  // S2ST_DEC_OVERLAP=<bit mask> (per call, default 3; 0 = everything below in tape order on the data path): mel-decoder work
-  // that does not depend on the encoder, or that the encoder's backward does not depend on, runs on the second stream
-  //   bit 0  forward: prenet, positions, layer 0's self-attention block and cross-attention query projection read only
-  //          prev_output_tokens -- issued on the second stream ahead of the encoder (forward(): dec_early)
-  //   bit 1  backward: everything of layer 0 below its cross-attention's dK|dV (query projection ... prenet) produces
-  //          parameter gradients only -- tape range [tail_lo_idx, tail_hi_idx) on the second stream
-  // (A third piece was built and measured: each hoisted K|V projection's backward on the second stream right behind its
-  //  layer's cross-attention.  The data path then has to wait for the encoder output's gradient behind the second stream's
-  //  backlog of weight-gradient products, ~0.75 ms at that point of the step: +0.26 ms per step, left out --
-  //  profiles/r07_dec_overlap_pieces_ab.txt.)
-  int dec_overlap = 3;
-  hipEvent_t ev_head_ = nullptr;    // the block issued ahead (bit 0) is complete
-  // every event of the second stream was created (by the calls' results, not by the handles: the CPU emulator's events are
-  // null handles, and S2ST_DEC_OVERLAP has to engage there for tests/test_decoder_overlap.py to check its re-ordering)
-  bool side_events_ = false;
-  size_t tail_lo_idx = 0, tail_hi_idx = 0;
-  bool tail_bwd_on_side = false, tail_side_ = false;  // tail_side_: st_ points at the second stream for the tail's closures
-  bool dec_early_active = false;    // the last forward issued the block ahead, on the second stream (s2st_engine_dec_overlap_active)
-  size_t xattn0_idx = 0;            // tape index of the closure of mel-decoder layer 0's cross-attention (0: none)
-  bool side_used = false;
-  float* skws_side = nullptr;
-  bool side_allowed = false;  // bf16-operand mode and no S2ST_NO_SIDE_STREAM=1
-  bool side_tried = false;
-  void ensure_side() {        // the second stream and its events, on first need (the first training forward; the overlapped update)
-    if (side_ || side_tried || !side_allowed) return;
-    side_tried = true;
-    // the side stream carries weight gradients nobody waits for until the segment ends: lowest queue priority, so that
-    // when both queues have workgroups ready the data path (the critical chain of the backward) is dispatched first
-    int pr_least = 0, pr_greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest) != hipSuccess) pr_least = 0;
-    if (hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, pr_least) != hipSuccess) side_ = nullptr;
-    // No stream priorities: a plain second stream carries the same schedule.  This is also what gives the CPU emulator
-    // (tests/hipemu: its priority form always fails) a second stream at all -- a label there, every launch is synchronous --
-    // so the emulator suite now walks the second-stream schedule (aux heads, hoisted K|V projections, weight-gradient forks,
-    // S2ST_DEC_OVERLAP) in its issue order instead of the one-stream one.
-    if (!side_ && hipStreamCreateWithFlags(&side_, hipStreamNonBlocking) != hipSuccess) side_ = nullptr;
-    bool ev_ok = side_ != nullptr;
-    if (side_ && hipEventCreateWithFlags(&ev_kv_, hipEventDisableTiming) != hipSuccess) { ev_kv_ = nullptr; ev_ok = false; }
-    if (side_ && hipEventCreateWithFlags(&ev_head_, hipEventDisableTiming) != hipSuccess) { ev_head_ = nullptr; ev_ok = false; }
-    if (side_ && (hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming) != hipSuccess ||
-                  hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming) != hipSuccess ||
-                  hipEventCreateWithFlags(&ev_taps_, hipEventDisableTiming) != hipSuccess ||
-                  hipEventCreateWithFlags(&ev_auxb_, hipEventDisableTiming) != hipSuccess)) {
-      hipStreamDestroy(side_);
-      side_ = nullptr;
-    }
-    side_events_ = side_ && ev_ok;
-  }
-  hipStream_t fork_side() {  // everything issued on st_ so far happens-before what follows on the returned stream
-    if (!side_) return st_;
-    hipEventRecord(ev_fork_, st_);
-    hipStreamWaitEvent(side_, ev_fork_, 0);
-    side_used = true;
-    return side_;
-  }
-  // S2ST_STALL_TRACE=1: time spent by the data-path stream in each cross-stream wait (timing events around the
-  // wait; read back by s2st_engine_stall_report after the caller synchronised)
-  struct Stall { const char* what; hipEvent_t a, b; };
-  std::vector<Stall> stalls;
-  bool stall_trace = false;
-  void wait_traced(hipStream_t st, hipEvent_t ev, const char* what) {
-    if (!stall_trace) { hipStreamWaitEvent(st, ev, 0); return; }
-    Stall s{what, nullptr, nullptr};
-    hipEventCreate(&s.a);
-    hipEventCreate(&s.b);
-    hipEventRecord(s.a, st);
-    hipStreamWaitEvent(st, ev, 0);
-    hipEventRecord(s.b, st);
-    stalls.push_back(s);
-  }
-  void join_side() {
-    if (!side_ || !side_used) return;
-    hipEventRecord(ev_join_, side_);
-    wait_traced(st_, ev_join_, "join_side");
-    side_used = false;
-  }
-
-  // ---- AR decoding state (config 5): caller-owned cache buffer laid out by decode_begin --------
-  // replay_ != null: decode_step in its graph-replayable form (s2st_engine_decode_step_replay): the step, the prenet's dropout
-  // seeds, the input frame, the position row and the output rows are read from / written to the fixed device buffers of *replay_
-  const s2st_decode_replay* replay_ = nullptr;
-  // merged decode batches (s2st_engine_decode_row_map): device [B] -- the row of its OWN batch whose Prenet dropout mask row b draws
-  const int* dec_row_map = nullptr;
-  bool stop_after_encoder = false;
-  Ten* enc_out_keep = nullptr;
-  struct Dec {
-    float* base = nullptr; int B = 0, E = 0, maxT = 0; const int* enc_lens = nullptr; const float* pe_dec = nullptr;
-    float* pe_alpha = nullptr;  // [maxT + 2][dec_dim]: pos_emb_alpha * PE rows (tail of the caller's state buffer)
-  } dec_st;
-  float* dec_selfK(int l) const { return dec_st.base + (long)l * 2 * dec_st.B * dec_st.maxT * c.dec_dim; }
-  float* dec_selfV(int l) const { return dec_selfK(l) + (long)dec_st.B * dec_st.maxT * c.dec_dim; }
-  float* dec_crossKV(int l) const {
-    return dec_st.base + (long)c.dec_layers * 2 * dec_st.B * dec_st.maxT * c.dec_dim + (long)l * dec_st.B * dec_st.E * 2 * c.dec_dim;
-  }
-  bool use_ln_skinny = true; // S2ST_NO_LN_SKINNY=1 (A/B switch): separate layer-norm kernels in the AR decoding steps
-  bool use_skinny = true;    // S2ST_NO_SKINNY=1 (A/B switch): tiled GEMMs for the AR decoding steps too
-  bool use_ln_fuse = true;  // S2ST_NO_LN_FUSE=1 (A/B switch): separate dropout-backward prologue pass
-  bool use_only_h = true;  // S2ST_NO_ONLY_H=1: always keep the fp32 copy of GEMM-only tensors (A/B switch)
-  // S2ST_ATTN_GFUSE (default 1): the attention backward emits the bf16 projection gradients itself (no fp32 gradient, no
-  // cast pass: ~30 launches fewer on the data path); the modes differ in where the projections' bias gradients come from
-  // (attention block below).  1 (default since round 3): out of the kernels' fp32 accumulators BEFORE rounding, as per-(block,
-  // wave) partial sums by DPP row reductions, folded in a fixed order with the segment's layer-norm partials -- exact (a key
-  // bias's mathematically zero gradient stays ~0) and run-to-run identical; 2: the same sums as fp32 atomics; 3: column sums of
-  // the ROUNDED copies (round 1's form: a rounding residue instead of ~0 that changes with any upstream ulp -- multi-update
-  // trajectories of cold processes then repeat in ~85 % of runs); 0: off (fp32 gradients + cast pass).
-  bool use_attn_gfuse = true;
-  int attn_gfuse_mode = 1;
-  // Ordered sums (default since round 3; S2ST_ORDERED_BIAS_SUMS=0 restores the atomics, an A/B switch): every sum that
-  // used fp32 atomics -- bias-gradient column sums (linear backward prologue, conv biases, the masked data-gradient
-  // GEMM epilogue), embedding-row gradients, the decoder's position scale -- is formed as partial rows + a fold in index
-  // order, so a gradient is a function of (parameters, batch, seed) down to the last bit.  Round 2 had this as an
-  // option at +3 % of a step (one small fold launch per sum); the folds now ride in the segment's batched fold launch
-  // (pending_lnfold), i.e. cost no launches of their own.
-  bool ordered_sums = true;
-  bool use_act_fuse = true;  // S2ST_NO_ACT_FUSE=1: separate ReLU-dropout backward kernel (A/B switch)
-  bool use_flash = true;  // S2ST_NO_FLASH=1: unfused attention everywhere (A/B switch)
-  // S2ST_ATTN_KEEP_F32=1 (A/B switch): the fused attention also stores O in fp32 and the out-projection's data-gradient
-  // GEMM also stores dO in fp32, although every reader takes the bf16 copies
-  bool attn_keep_f32 = s2st_env_on("S2ST_ATTN_KEEP_F32");
-  // S2ST_CONVNET_FUSE=0 (A/B switch): BatchNorm statistics finalize / backward fold / the convolutions' gradient halo
-  // images / the post-net residual add as launches of their own
-  bool convnet_fuse = s2st_env_int("S2ST_CONVNET_FUSE", 1) != 0;
-  int ffn_act = 1;        // 1 relu (s2st layers), 2 gelu (the speech encoders' layers)
-  // what the handle was created as: the s2st / s2t transformer, or one of the frozen forward-only networks in the same
-  // engine object (engine_speech_encoder.h, engine_hifigan.h)
-  enum class Kind { Transformer, SpeechEncoder, HifiGan };
-  Kind kind = Kind::Transformer;
-  float* ws_for(hipStream_t s) const { return (side_ && s == side_) ? skws_side : skws; }
-  float* skws = nullptr;  // split-K partial-sum scratch of the weight-gradient GEMMs (per call)
-  long skws_n = 0;
-  bool ph_fresh = false;   // s2st_engine_bf16_is_fresh: PH already equals bf16(P) for the next forward
-  bf16raw* PHT = nullptr;  // optional: transposed bf16 copies of the 2-D weights (same offsets): the
-                           // data-gradient GEMMs then read K-contiguous operands (~25 % faster here)
-  bool pht_valid = false;
-  struct WT { long off; int N, K; };
-  std::vector<WT> wt_list;  // the [N][K] matrices linear() multiplies by (fused k|v|q blocks as ONE matrix)
-  void reg_wt(long off, int N, int K) { if (N % 8 == 0 && K % 8 == 0) wt_list.push_back(WT{off, N, K}); }
-  bool has_wt(long off, int N, int K) const {
-    if (!pht_valid) return false;
-    for (const WT& t : wt_list) if (t.off == off && t.N == N && t.K == K) return true;
-    return false;
-  }
-  std::vector<s2st_transpose_table> wt_tables;
-  void build_wt_tables() {
-    s2st_transpose_table cur{};
-    for (const WT& t : wt_list) {
-      if (cur.n == S2ST_TRANSPOSE_MAX) { wt_tables.push_back(cur); cur = s2st_transpose_table{}; }
-      const int i = cur.n++;
-      cur.off[i] = (unsigned)t.off; cur.rows8[i] = (unsigned short)(t.N / 8); cur.cols8[i] = (unsigned short)(t.K / 8);
-      cur.tile0[i + 1] = cur.tile0[i] + (unsigned)(((t.N + 63) / 64) * ((t.K + 63) / 64));
-    }
-    if (cur.n) wt_tables.push_back(cur);
-  }
-  bf16raw* PH = nullptr;  // bf16 copy of the parameter arena (same offsets), refreshed every forward
-  bool f32_operands = false;  // debug A/B switch S2ST_F32_OPERANDS=1: bf16 MFMA on fp32-stored operands
-  bool fast() const { return c.precise == 0 && !f32_operands; }
-
-  // parameter handles
-  ConvP sub[2];
-  std::vector<EncLayerP> enc;
-  LNP enc_ln; bool has_enc_ln = false;
-  LNP asr_norm, st_norm;
-  long pos_alpha = 0;
-  std::vector<LinP> prenet;   // prenet_layers + 1
-  std::vector<DecLayerP> dec;
-  LNP dec_ln; bool has_dec_ln = false;
-  LinP feat_proj, eos_proj;
-  std::vector<ConvP> post_conv;
-  std::vector<BNP> post_bn;
-  LinP ctc_proj, ctc_proj_tgt;
-  AuxP asr, st;
-  AuxP s2t;  // s2t_mode: the model's own text decoder ("decoder.*")
-
-  // per-call state
-  float* ws = nullptr;
-  long ws_cap = 0, ws_top = 0, ws_peak = 0;
-  bool dry = false, oom = false;
-  int err = 0;
-  hipStream_t st_ = nullptr;
-  std::vector<std::function<void()>> tape;
-  std::vector<Ten*> tens;
-  struct Mark { size_t tape_idx; long param_off; };
-  std::vector<Mark> marks;
-  long param_watermark = 0;
-  int next_segment = 0;
-  uint64_t seed = 0, site = 0;
-  float gscale = 1.f;
-  s2st_batch bt;
-  s2st_outputs outs;
-
-#include "engine_params.h"  // parameter construction
-
-#include "engine_runtime.h"  // per-call runtime
-
-#include "engine_ops.h"  // the ops of the training graph
-
-#include "engine_decode.h"  // incremental decoding
-
-#include "engine_convnets.h"  // the convolutional sub-networks
-
-#include "engine_speech_encoder.h"  // the frozen HuBERT front end (config 4) and the wav2vec 2.0 CTC recogniser (ASR-BLEU)
-
-#include "engine_hifigan.h"  // the HiFi-GAN vocoder (--vocoder hifigan)
-
-#include "engine_step.h"  // one step
-
-};
+using namespace s2st_eng;
 
 namespace {
 // The workspace a call needs: `body` runs in dry mode (sizes every allocation, launches nothing) on a workspace that is
@@ -350,7 +46,42 @@ bool aux_args_ok(const s2st_engine* e, int which) {
   return e && which >= 0 && which <= 1 && !((which == 0 && !e->c.has_asr) || (which == 1 && !e->c.has_st));
 }
 
-// The two speech encoders' one create (engine_speech_encoder.h): cfg.vocab is read by the LayerNormPreLN variant only.
+// The one place that reads the environment into the engine's table of switches (s2st_engine::Switches, where every field is
+// documented).  Called once by each create path; a kind reads what it read before there was a table -- the rest of the
+// table stays at its defaults.  (S2ST_DEC_OVERLAP is read per call by forward(); S2ST_CHAINS is checked by s2st_engine_create.)
+void read_switches(s2st_engine::Switches& sw, s2st_engine::Kind kind) {
+  // every kind
+  sw.attn_keep_f32 = s2st_env_on("S2ST_ATTN_KEEP_F32");
+  sw.convnet_fuse = s2st_env_int("S2ST_CONVNET_FUSE", 1) != 0;
+  sw.use_streamk = s2st_env_on("S2ST_GEMM_STREAMK");
+  if (kind == s2st_engine::Kind::HifiGan) return;
+  // the transformer and the speech encoders
+  sw.f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
+  sw.use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
+  if (kind == s2st_engine::Kind::SpeechEncoder) return;
+  // the transformer
+  sw.group_wgrad = !(s2st_env_on("S2ST_NO_WGRAD_GROUP"));
+  if (s2st_env_str("S2ST_WGRAD_GROUP")) {
+    sw.group_flush_at = atoi(s2st_env_str("S2ST_WGRAD_GROUP"));
+    if (sw.group_flush_at < 1) sw.group_flush_at = 1;
+    if (sw.group_flush_at > S2ST_GROUP_MAX) sw.group_flush_at = S2ST_GROUP_MAX;
+  }
+  sw.use_act_fuse = !(s2st_env_on("S2ST_NO_ACT_FUSE"));
+  sw.use_only_h = !(s2st_env_on("S2ST_NO_ONLY_H"));
+  sw.hoist_kv = !(s2st_env_on("S2ST_NO_KV_HOIST"));
+  sw.stall_trace = s2st_env_on("S2ST_STALL_TRACE");
+  sw.use_ln_skinny = !(s2st_env_on("S2ST_NO_LN_SKINNY"));
+  sw.use_skinny = !(s2st_env_on("S2ST_NO_SKINNY"));
+  sw.use_ln_fuse = !(s2st_env_on("S2ST_NO_LN_FUSE"));
+  sw.attn_gfuse_mode = s2st_env_int("S2ST_ATTN_GFUSE", 1);
+  sw.use_attn_gfuse = sw.attn_gfuse_mode != 0;
+  sw.ln_bwd_split = s2st_env_on("S2ST_LN_BWD_SPLIT");
+  sw.ordered_sums = !(s2st_env_int("S2ST_ORDERED_BIAS_SUMS", 1) == 0);
+  sw.side_stream = !(s2st_env_on("S2ST_NO_SIDE_STREAM"));
+  sw.overlap_aux = !(s2st_env_on("S2ST_NO_AUX_OVERLAP"));
+}
+
+// The two speech encoders' one create (engine_speech_encoder.cpp): cfg.vocab is read by the LayerNormPreLN variant only.
 int speech_encoder_create(const s2st_w2v_ctc_config& cfg, s2st_engine::SpeechVariant v, s2st_engine** out) {
   const bool pre_ln = v == s2st_engine::SpeechVariant::LayerNormPreLN;
   if (cfg.n_conv < 1 || cfg.n_conv > 8 || (pre_ln && cfg.vocab < 1) || cfg.layers < 0 || cfg.heads < 1 ||
@@ -380,11 +111,10 @@ int speech_encoder_create(const s2st_w2v_ctc_config& cfg, s2st_engine::SpeechVar
   e->c.enc_heads = cfg.heads;
   e->c.enc_dim = cfg.embed;
   e->ffn_act = 2;
+  read_switches(e->sw, e->kind);
   // the recogniser: every product goes through the tiled GEMM whatever the batch's row count: an utterance's logits do not
   // depend on what else is in the batch
-  if (pre_ln) e->use_skinny = false;
-  e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
-  e->use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
+  if (pre_ln) e->sw.use_skinny = false;
   e->build_params_speech();
   // (a process that replays HIP graphs can carry a stale "last error" of the runtime's own capture-time queries: the preload's
   //  launch checks must see their own errors only)
@@ -415,25 +145,7 @@ int s2st_engine_create(const s2st_model_config* cfg, s2st_engine** out) {
   if (cfg->guided && (cfg->s2t_mode || cfg->dec_layers <= 0 || !(cfg->guided_sigma > 0.f))) return S2ST_ERR_ARG;
   s2st_engine* e = new s2st_engine();
   e->c = *cfg;
-  e->f32_operands = s2st_env_on("S2ST_F32_OPERANDS");
-  e->use_flash = !(s2st_env_on("S2ST_NO_FLASH"));
-  e->group_wgrad = !(s2st_env_on("S2ST_NO_WGRAD_GROUP"));
-  if (s2st_env_str("S2ST_WGRAD_GROUP")) {
-    e->group_flush_at = atoi(s2st_env_str("S2ST_WGRAD_GROUP"));
-    if (e->group_flush_at < 1) e->group_flush_at = 1;
-    if (e->group_flush_at > S2ST_GROUP_MAX) e->group_flush_at = S2ST_GROUP_MAX;
-  }
-  e->use_act_fuse = !(s2st_env_on("S2ST_NO_ACT_FUSE"));
-  e->use_only_h = !(s2st_env_on("S2ST_NO_ONLY_H"));
-  e->hoist_kv = !(s2st_env_on("S2ST_NO_KV_HOIST"));
-  e->stall_trace = s2st_env_on("S2ST_STALL_TRACE");
-  e->use_ln_skinny = !(s2st_env_on("S2ST_NO_LN_SKINNY"));
-  e->use_skinny = !(s2st_env_on("S2ST_NO_SKINNY"));
-  e->use_ln_fuse = !(s2st_env_on("S2ST_NO_LN_FUSE"));
-  e->attn_gfuse_mode = s2st_env_int("S2ST_ATTN_GFUSE", 1);
-  e->use_attn_gfuse = e->attn_gfuse_mode != 0;
-  e->ln_bwd_split = s2st_env_on("S2ST_LN_BWD_SPLIT");
-  e->ordered_sums = !(s2st_env_int("S2ST_ORDERED_BIAS_SUMS", 1) == 0);
+  read_switches(e->sw, e->kind);
   e->build_params();
   // (a process that replays HIP graphs can carry a stale "last error" of the runtime's own capture-time queries: the preload's
   //  launch checks must see their own errors only)
@@ -442,8 +154,7 @@ int s2st_engine_create(const s2st_model_config* cfg, s2st_engine** out) {
   // The second stream is made at the first TRAINING forward (ensure_side), not here: a process has four hardware queues
   // (runtime/streams.py) and an engine that only ever decodes would hold one of them for nothing -- the caller's stream
   // then shares a queue with one of the generator's chains (config 5, profiles/r05_queue_matrix.txt).
-  e->side_allowed = !cfg->precise && !(s2st_env_on("S2ST_NO_SIDE_STREAM"));
-  e->overlap_aux = !(s2st_env_on("S2ST_NO_AUX_OVERLAP"));
+  e->side_allowed = !cfg->precise && e->sw.side_stream;
   *out = e;
   return 0;
 }
@@ -688,10 +399,10 @@ int s2st_engine_decode_step(s2st_engine* e, int32_t step, const float* prev, con
 // 1 when the run decode_begin prepared is made of the forms decode_step_replay can take (bf16-operand mode, skinny products
 // for <= 64 utterances, the position row and the logistic fused): the conditions decode_step itself checks, asked up front
 int32_t s2st_engine_decode_replay_supported(const s2st_engine* e) {
-  if (!e || !e->dec_st.base || !e->dec_st.pe_alpha || !e->fast() || !e->PH || !e->use_skinny) return 0;
+  if (!e || !e->dec_st.base || !e->dec_st.pe_alpha || !e->fast() || !e->PH || !e->sw.use_skinny) return 0;
   const int B = e->dec_st.B, Cd = e->c.dec_dim;
   if (B < 1 || B > 64 || e->c.prenet_dim % 32 || e->c.out_dim % 32 || Cd % 64 || e->c.prenet_layers > 7) return 0;
-  if (e->has_dec_ln && !e->use_ln_skinny) return 0;
+  if (e->has_dec_ln && !e->sw.use_ln_skinny) return 0;
   return 1;
 }
 
@@ -893,6 +604,7 @@ int s2st_hifigan_create(const s2st_hifigan_config* cfg, s2st_engine** out) {
   e->gc = *cfg;
   e->c = s2st_model_config{};
   e->c.precise = cfg->precise;
+  read_switches(e->sw, e->kind);
   e->build_params_hifigan();
   *out = e;
   return 0;

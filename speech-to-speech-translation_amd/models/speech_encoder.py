@@ -1,5 +1,5 @@
 """What the two frozen wav2vec 2.0-family encoders share on the host: the HuBERT front end (models/hubert.py) and the
-wav2vec 2.0 CTC recogniser (models/wav2vec2_ctc.py) are one architecture in the engine (csrc/engine_speech_encoder.h), so
+wav2vec 2.0 CTC recogniser (models/wav2vec2_ctc.py) are one architecture in the engine (csrc/engine_speech_encoder.cpp), so
 they are one geometry, one table of reference shapes, one loader core and one frame count here.  A subclass names its
 convolution weights (``CONV_W``) and its positional convolution's weight (``POS_W``) and keeps what is its own.
 

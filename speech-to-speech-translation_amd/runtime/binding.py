@@ -231,7 +231,7 @@ def flash_attention(q, k, v, H, *, klen=None, causal=False, scale=None, drop_p=0
     leaves the bf16 copy of o (what the engine does); the backward then forms D = rowsum(dO * o) inside its kernels from
     the bf16 copies instead of running the fp32 row kernel first.
 
-    The keyword options after ``scratch`` reproduce the calling conventions of the training step (engine_ops.h):
+    The keyword options after ``scratch`` reproduce the calling conventions of the training step (engine_ops.cpp):
 
     * ``layout``: "dense" (three tensors), "self" (q / k / v are column blocks of ONE packed projection [K|V|Q], T == S) or
       "cross" (dense q, k / v column blocks of a packed [K|V]); the gradients are written in the same layout.  ``pad``:

@@ -140,7 +140,7 @@ def test_flash_attention_bench_head_geometry(backend, T, S, causal):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# The kernels as the training step calls them (engine_ops.h: attention(), self_attn_block, cross_attn_block): q / k / v are
+# The kernels as the training step calls them (engine_ops.cpp: attention(), self_attn_block, cross_attn_block): q / k / v are
 # column blocks of a packed projection ([K|V|Q] with ld = 3C for self-attention, dense q + [K|V] with ld = 2C for
 # cross-attention), only the bf16 copies of O and of the gradients are stored, the bias gradients leave as per-(block, wave)
 # partial sums, and attention dropout is on -- its mask recomputed in every backward body.

@@ -1,4 +1,4 @@
-"""S2ST_DEC_OVERLAP (csrc/engine.cpp, engine_step.h): mel-decoder work that does not depend on the encoder -- the prenet,
+"""S2ST_DEC_OVERLAP (csrc/engine.h, engine_step.cpp): mel-decoder work that does not depend on the encoder -- the prenet,
 the positions, layer 0's self-attention block and cross-attention query projection in the forward; everything of layer 0
 below its cross-attention's dK|dV in the backward -- is issued on the engine's second stream, beside the encoder.  The same kernels run with the same arguments; only the stream and the place in the
 enqueue order differ.  So a step with the overlap (mask 3, the default; 1 / 2 = its two pieces alone) must be the

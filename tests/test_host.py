@@ -31,6 +31,37 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.s2st_version() >= 100
 
 
+def test_engine_header_compiles_alone_and_no_struct_fragments(tmp_path):
+    """csrc/engine.h is a real header: a unit that includes nothing else passes the emulator build's compiler
+    (tests/hipemu/build_emu.sh: its compiler, its include paths and defines) with -fsyntax-only.  And no file of csrc/
+    is pasted into a struct body again: an indented ``#include "..."`` of a project file is what that looked like."""
+    import re
+    import subprocess
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    here = os.path.join(ROOT, "tests", "hipemu")
+    script = open(os.path.join(here, "build_emu.sh")).read()
+    m_cxx = re.search(r"^CXX=(\S+)$", script, re.M)
+    m_flags = re.search(r'^FLAGS="([^"]*)"$', script, re.M)
+    assert m_cxx and m_flags, "build_emu.sh no longer has one-line CXX= / FLAGS=\"...\": teach this test its new form"
+    cxx = m_cxx.group(1)
+    flags = m_flags.group(1).replace("$HERE", here).replace("$SRC", csrc).replace("$ROOT", ROOT).split()
+    assert any(f.startswith("-I") for f in flags)
+    probe = tmp_path / "engine_h_alone.cpp"
+    probe.write_text('#include "engine.h"\nint main() { return 0; }\n')
+    r = subprocess.run([cxx] + flags + ["-x", "c++", "-fsyntax-only", str(probe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    # (deliberately strict: an include of a project file indented inside an #if block is rejected too -- csrc/ keeps its
+    #  includes at column 0, and a scan that tracked braces would be more machinery than the rule is worth)
+    pasted = []
+    for f in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, f)
+        if os.path.isfile(path) and f.endswith((".h", ".cpp", ".hip")):
+            for n, line in enumerate(open(path, errors="replace"), 1):
+                if re.match(r'\s+#include "', line):
+                    pasted.append("%s:%d" % (f, n))
+    assert not pasted, pasted
+
+
 @pytest.mark.parametrize("backend", ["emu"], indirect=True)
 def test_every_called_entry_point_is_declared_and_bound(backend):
     """The package reaches the library only through names include/s2st_hip.h declares (``lib.<name>``,

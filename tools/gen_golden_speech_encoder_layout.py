@@ -6,7 +6,7 @@ order, offsets and shapes of the parameter arena, and `s2st_*_workspace_floats` 
 sizes of the forward's workspace allocations show in it.
 
 Recording procedure (the expected values come from the commit BEFORE the two engines were merged into
-csrc/engine_speech_encoder.h, 9ea59fe, never from the code under test):
+what is now csrc/engine_speech_encoder.cpp, 9ea59fe, never from the code under test):
   1. in a scratch copy of that commit, tests/hipemu/build_emu.sh;
   2. python tools/gen_golden_speech_encoder_layout.py --record <that libs2st_emu.so>
 Nothing is launched: the parameter tables come from `precise = 1` handles with no arena bound, the workspace sizes from the
